@@ -1,8 +1,19 @@
 #!/usr/bin/env python
 """Headline benchmark: images/sec (whole node), ResNet-18 224x224 training, 1/2/4/8 MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     torchrun --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N ...
+
+A plain run does only what the headline figure needs: set up, W warm-up steps, K timed
+steps, the optional output dump, one JSON line.  ``--full`` adds everything else the
+benchmark measures: the HBM bandwidth probe before the model is built, the multi-GPU
+decision variants and the small-batch pass (a second, complete JSON line follows them).
+``--dump-outputs DIR`` writes what the last timed step computed (its loss, the gradients it
+left in the arena and the fp32 master weights after its optimizer update) as
+``DIR/<name>.npy``; weights, batches and the dumped sample are seeded and the kernels run
+in deterministic mode (fixed-order reductions, static GEMM tiles: MPA_DETERMINISTIC), so
+a run repeats bitwise and two builds run with the same arguments can be compared output
+for output.
 
 Config (BASELINE.json): ResNet-18 with the reference's 64,500-class head (utils.py:39),
 224x224 synthetic uint8 images (preprocessed on the GPU each step), random-init weights,
@@ -23,7 +34,7 @@ hangs forever on a lost peer):
     parallel/watchdog.py): a rank whose GPU stops completing steps dumps its stacks and exits
     75 with a rank-tagged message, and the launcher tears the job down;
   * the headline record is built AND PRINTED (flushed) right after the timed steps, before
-    any optional extra runs.  The extras after it (multi-GPU decision variants, the
+    any optional extra runs.  The extras after it (--full: multi-GPU decision variants, the
     small-batch pass) each run in try/except, all under one wall-clock budget
     (--extras-budget); when they finish, rank 0 prints a second, complete record (the same
     headline fields plus the extras).  An extra's exception is recorded in that record
@@ -52,6 +63,8 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 BASELINE_IMG_S = 8.06  # reference FLOP-equivalent img/s at 224^2 (best, 4 ranks)
+DUMP_MAX_ELEMS = 1 << 22  # --dump-outputs: elements written per array (16 MiB of float32)
+DUMP_SEED = 20240229      # seed of the sample taken from a larger array
 
 
 def _emulate_comm(model, step, spec, dev, reserve=0):
@@ -96,6 +109,16 @@ def parse_args(argv=None):
                    help="cpu: plumbing check of the same code path on host ops (gloo for N>1)")
     p.add_argument("--steps", type=int, default=20)
     p.add_argument("--warmup", type=int, default=5)
+    p.add_argument("--full", action="store_true",
+                   help="besides the headline measurement, run everything else the benchmark "
+                        "measures: the HBM bandwidth probe at start, the multi-GPU decision "
+                        "variants (--decisions) and the small-batch pass (--small-batch)")
+    p.add_argument("--dump-outputs", default="", metavar="DIR",
+                   help="after the timed steps, write what the last of them computed to "
+                        "DIR/<name>.npy (float32): loss, grads, params - the latter two a "
+                        "fixed seeded sample of the flat arenas when those are larger than "
+                        "%d elements.  The run is made in deterministic mode "
+                        "(MPA_DETERMINISTIC), so that it repeats bitwise" % DUMP_MAX_ELEMS)
     p.add_argument("--batch", type=int, default=2048,
                    help="per-GPU batch (profiles/batch_sweep_r6.txt, one MI355X, same box: 1024 -> "
                         "53.3k, 1536 -> 54.9k, 2048 -> 54.7-55.5k img/s; ~57 GB of the 288 GB "
@@ -121,7 +144,7 @@ def parse_args(argv=None):
                         "to the emulated collective while it is in flight")
     p.add_argument("--profile-steps", type=int, default=0)
     p.add_argument("--small-batch", type=int, default=128,
-                   help="after the headline measurement, also time --steps steps at this "
+                   help="--full: after the headline measurement, also time --steps steps at this "
                         "per-GPU batch (the reference's utils.py:40 BATCH_SIZE), eager and - "
                         "on one GPU - HIP-graph replayed; reported as 'small_batch' (0: off)")
     p.add_argument("--print-losses", action="store_true", help="debug: sync + print each loss")
@@ -137,7 +160,7 @@ def parse_args(argv=None):
                         "data-parallel all-reduce overlapping backward); the optimizer waits "
                         "for it like for the real collective")
     p.add_argument("--decisions", type=int, default=1,
-                   help="more than one GPU: after the headline, also time the capped-communicator "
+                   help="--full, more than one GPU: after the headline, also time the capped-communicator "
                         "+ reservation and bf16-wire variants and probe the all-reduce bandwidth "
                         "('multi_gpu' in the JSON; 0: off)")
     p.add_argument("--pg-timeout", type=float, default=240.0,
@@ -218,6 +241,60 @@ def _gpu_busy():
             pass
         vals.append([d.split("/")[-2], busy, clk])
     return vals or None
+
+
+def _dump_outputs(path: str, loss, arena) -> dict:
+    """--dump-outputs: what the last timed step handed back, as float32 ``path/<name>.npy``:
+    ``loss`` (its return value), ``grads`` (the flat gradient arena it filled, after the
+    all-reduce) and ``params`` (the fp32 master weights after its optimizer update).  An
+    arena of more than DUMP_MAX_ELEMS elements is sampled at sorted indices drawn from a
+    fixed seed, the same for every run of the same model.  Returns name -> shape."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrays = {"loss": loss.detach().reshape(1)}
+    for name, t in (("grads", arena.grad), ("params", arena.master)):
+        n = t.numel()
+        if n > DUMP_MAX_ELEMS:
+            idx = np.sort(np.random.default_rng(DUMP_SEED).integers(0, n, size=DUMP_MAX_ELEMS))
+            t = t.detach().index_select(0, torch.from_numpy(idx).to(t.device))
+        arrays[name] = t.detach()
+    shapes = {}
+    for name, t in arrays.items():
+        a = t.to(device="cpu", dtype=torch.float32).contiguous().numpy()
+        np.save(os.path.join(path, name + ".npy"), a)
+        shapes[name] = list(a.shape)
+    return shapes
+
+
+class _Pace:
+    """Bounds how far the host runs ahead of the device: after each step, ``step()`` records
+    an event and waits for the one recorded MAX_LEAD steps earlier.
+
+    Nothing in a step synchronizes, and at the headline batch the host enqueues a step in
+    a tenth of the time the GPU takes to run it.  Tensors that crossed streams (the
+    prefetcher's image batch, every conv's x and dz read by the weight-gradient stream) are
+    record_stream'ed, so their memory returns only once the device has passed the step:
+    each step the host is ahead holds tens of GB at batch 2048, and a long run would lean
+    on the allocator's out-of-memory retry.  With MAX_LEAD steps always queued the GPU
+    never waits for the host; the wait is a blocking one, leaving the CPU to the ring's
+    producers."""
+
+    MAX_LEAD = 2
+
+    def __init__(self, device, event_factory=None):
+        self.cuda = torch.device(device).type == "cuda"
+        # (a stand-in factory lets the bookkeeping be tested without a GPU)
+        self._event = event_factory or (lambda: torch.cuda.Event(blocking=True))
+        self._events = []
+
+    def step(self) -> None:
+        if not self.cuda:
+            return
+        ev = self._event()
+        ev.record()
+        self._events.append(ev)
+        if len(self._events) > self.MAX_LEAD:
+            self._events.pop(0).synchronize()
 
 
 def _inject() -> str:
@@ -314,9 +391,11 @@ def _timed(step, data, args, world, sync) -> float:
     like the headline measurement (barrier + device sync, max time over ranks)."""
     from mpi_pytorch_amd.parallel import barrier
     from mpi_pytorch_amd.engine import steps_without_gc
+    pace = _Pace(world.device)
     for _ in range(max(args.warmup, 2)):
         x, y = data.next()
         step(x, y)
+        pace.step()
     # the training driver's loop policy: cyclic GC at the boundaries, not mid-step
     with steps_without_gc():
         sync()
@@ -326,6 +405,7 @@ def _timed(step, data, args, world, sync) -> float:
         for _ in range(args.steps):
             x, y = data.next()
             step(x, y)
+            pace.step()
         sync()
         barrier()
         sync()
@@ -346,12 +426,14 @@ def _variant(step, data, args, world, sync, configure, restore) -> dict:
     from mpi_pytorch_amd.parallel import barrier
     from mpi_pytorch_amd.engine import steps_without_gc
     info = configure() or {}
+    pace = _Pace(world.device)
     try:
         if _inject() == "variant_raise":
             raise RuntimeError("injected variant failure")
         for _ in range(max(min(args.warmup, 3), 1)):
             x, y = data.next()
             step(x, y)
+            pace.step()
         if step.timer is not None:
             step.timer.summary()  # (drop the warm-up steps)
         step.bucketer.enable_comm_stats()
@@ -363,6 +445,7 @@ def _variant(step, data, args, world, sync, configure, restore) -> dict:
             for _ in range(args.steps):
                 x, y = data.next()
                 step(x, y)
+                pace.step()
             sync()
             barrier()
             sync()
@@ -477,15 +560,30 @@ def run(args) -> None:
     # device memory free at start (a previous process's memory still being released shows
     # here; see docs/NOTES.md "Slow processes")
     mem0 = [round(v / 2**30, 1) for v in torch.cuda.mem_get_info(dev)] if cuda else None
-    bw0 = _hbm_probe(dev) if cuda else None
+    bw0 = _hbm_probe(dev) if cuda and args.full else None
     from mpi_pytorch_amd.engine import reserve_device_memory
     share = max(1, -(-world.world_size // max(torch.cuda.device_count(), 1))) if cuda else 1
     reserved = reserve_device_memory(dev, args.reserve_gib / share)  # (ranks per GPU share it)
+    if cuda:
+        torch.cuda.reset_peak_memory_stats(dev)  # (the reservation is no peak of the run)
 
     def sync():
         if cuda:
             torch.cuda.synchronize()
 
+    deterministic = False
+    if cuda:
+        from mpi_pytorch_amd.ops import _ext
+        if args.dump_outputs:
+            # Outputs that are to be compared must repeat.  By default the BN cross-block
+            # sums combine by float atomics and the GEMM tiles come from timings, so two
+            # runs differ in the last bits of a step, and a deep BN net's training
+            # trajectory amplifies that to decorrelated gradients within tens of steps
+            # (docs/NOTES.md "Numerics").  Deterministic mode (fixed-order combines, static
+            # tiles) makes the run bitwise repeatable; measured cost 0.3 %, within the
+            # run-to-run spread (three alternating 100-step pairs).
+            _ext.ext().set_deterministic(1)
+        deterministic = bool(_ext.ext().deterministic())
     hw = (args.image_size, args.image_size)
     model, opt, step, _ = build_training(args.model, args.classes, dev, world, args.lr,
                                          args.optimizer, bucket_mb=args.bucket_mb,
@@ -510,9 +608,11 @@ def run(args) -> None:
     inject = _inject()
     hang_rank = int(inject.split("=", 1)[1]) if inject.startswith("hang_rank=") else -1
     nbeat = [0]
+    pace = _Pace(dev)
 
     def beat():
         nbeat[0] += 1
+        pace.step()
         if args.watchdog > 0:  # re-arm the GIL-free backstop: it measures time since a beat
             faulthandler.dump_traceback_later(args.watchdog + 60.0, exit=True)
         if cuda:
@@ -556,6 +656,7 @@ def run(args) -> None:
     barrier()
     sync()
     cs0, cpu0 = _cpu_stat(), time.process_time()
+    last_loss = None
     t0 = time.perf_counter()
     for i in range(args.steps):
         if i == 1 and world.rank == hang_rank:
@@ -565,7 +666,7 @@ def run(args) -> None:
         x, y = data.next()
         if mk is not None:
             mk.range_pop()
-        step(x, y)
+        last_loss = step(x, y)
         beat()
     # (sampled while the device still runs the last queued steps; host side only;
     # MPA_BENCH_CARDS=1: every card of the host, a diagnostic of the slow-process study)
@@ -588,6 +689,10 @@ def run(args) -> None:
     imgs = args.steps * args.batch * world.world_size
     value = imgs / dt
     ring = data_stats(True)
+    dumped = None
+    if args.dump_outputs and world.rank == 0 and last_loss is not None:
+        # (every rank holds the same reduced gradients and weights: rank 0 writes them)
+        dumped = _dump_outputs(args.dump_outputs, last_loss, model._mpa_arena)
 
     # ---- the headline record, complete before any optional extra runs
     metric = "images/sec (whole node) ResNet-18 224x224 training at 1/2/4/8 MI355X"
@@ -619,6 +724,7 @@ def run(args) -> None:
             "device": args.device,
             "backend": world.backend,
             "hip_graph": bool(use_graph),
+            "deterministic": deterministic,
             "mean_loss": round(loss, 4),
         },
     }
@@ -631,6 +737,8 @@ def run(args) -> None:
         rec["comm"] = comm
     if ring is not None:
         rec["data_ring"] = ring
+    if dumped is not None:
+        rec["dumped_outputs"] = {"dir": args.dump_outputs, "shapes": dumped}
     host = {"process_cpu_s": round(cpu1 - cpu0, 3)}
     if "throttled_usec" in cs1:
         host["cgroup_throttled_ms"] = round((cs1["throttled_usec"] -
@@ -638,8 +746,10 @@ def run(args) -> None:
         host["cgroup_nr_throttled"] = cs1.get("nr_throttled", 0) - cs0.get("nr_throttled", 0)
     if mem0 is not None:
         host["device_free_total_gib_at_start"] = mem0
-        host["hbm_probe_at_start_gbps"] = bw0
+        if bw0 is not None:
+            host["hbm_probe_at_start_gbps"] = bw0
         host["reserved_gib"] = reserved
+        host["peak_allocated_gib"] = round(torch.cuda.max_memory_allocated(dev) / 2**30, 1)
         if cards is not None:
             host["cards_busy_sclk"] = cards
     rec["host"] = host
@@ -650,6 +760,11 @@ def run(args) -> None:
     # ---- the headline line goes out now: nothing after this point can lose it
     emitter = _Emitter(world.rank)
     emitter.headline(rec)
+    from mpi_pytorch_amd.parallel import shutdown
+    if not args.full:  # a plain run is done: the extras below belong to --full
+        data.close()
+        shutdown()
+        return
     # ---- optional extras, each guarded, all under one wall-clock budget
     timer = _deadline(args.extras_budget, emitter, world.rank)
     if inject == "extras_hang":
@@ -685,7 +800,6 @@ def run(args) -> None:
     if "multi_gpu" in rec or "small_batch" in rec:
         emitter.final(rec)
     data.close()
-    from mpi_pytorch_amd.parallel import shutdown
     shutdown()
 
 

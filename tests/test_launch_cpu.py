@@ -27,7 +27,7 @@ def test_bench_spawns_ranks_itself(tmp_path):
     rank 0 prints exactly one JSON line with n_gpus 2 and the per-bucket comm stats."""
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--device", "cpu",
            "--image-size", "32", "--batch", "2", "--classes", "10", "--steps", "2",
-           "--warmup", "1"]
+           "--warmup", "1", "--full"]
     r = subprocess.run(cmd, cwd=str(tmp_path), env=_env(), capture_output=True, text=True,
                        timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -74,7 +74,7 @@ def _bench_cpu(tmp_path, inject, extra=(), timeout=300):
     env["MPA_BENCH_INJECT"] = inject
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--device", "cpu",
            "--image-size", "32", "--batch", "2", "--classes", "10", "--steps", "3",
-           "--warmup", "1"] + list(extra)
+           "--warmup", "1", "--full"] + list(extra)
     t0 = time.time()
     r = subprocess.run(cmd, cwd=str(tmp_path), env=env, capture_output=True, text=True,
                        timeout=timeout)

@@ -28,7 +28,7 @@ def _env(**kw):
 def test_bench_two_ranks_one_gpu(gpu, tmp_path):
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--batch", "32",
            "--image-size", "64", "--classes", "1000", "--steps", "3", "--warmup", "1",
-           "--small-batch", "0"]
+           "--small-batch", "0", "--full"]
     r = subprocess.run(cmd, cwd=str(tmp_path), env=_env(), capture_output=True, text=True,
                        timeout=240)
     assert r.returncode == 0, r.stderr[-3000:]
