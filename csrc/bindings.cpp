@@ -1369,6 +1369,89 @@ void sgd_step(Tensor p, Tensor g, Tensor buf, Tensor shadow, Tensor step, double
                 momentum, dampening, wd, nesterov ? 1 : 0, gs, cur_stream());
 }
 
+// ---- per-step recipe: global gradient norm, hyper record, device-argument optimizers
+static void check_hyper(const Tensor& hyper, const Tensor& like) {
+  CHECK_F32(hyper);
+  TORCH_CHECK(hyper.is_contiguous() && hyper.numel() >= mpa::HYPER_N &&
+                  hyper.device() == like.device(), "hyper: fp32 [8] on the arena's device");
+}
+
+int64_t grad_sqnorm(Tensor g, Tensor part) {
+  CHECK_CUDA(g);
+  CHECK_CONTIG(g);
+  CHECK_F32(g);
+  CHECK_F32(part);
+  TORCH_CHECK(g.numel() % 4 == 0 && reinterpret_cast<uintptr_t>(g.data_ptr()) % 16 == 0,
+              "grad_sqnorm: numel % 4 == 0 and 16-B alignment required");
+  TORCH_CHECK(part.is_contiguous() && part.device() == g.device() &&
+                  part.numel() >= mpa::grad_sqnorm_grid_cap(),
+              "grad_sqnorm: workspace of at least grad_sqnorm_grid_cap() floats");
+  const c10::OptionalDeviceGuard gd(device_of(g));
+  return mpa::grad_sqnorm(g.data_ptr<float>(), g.numel(), part.data_ptr<float>(), cur_stream());
+}
+
+void grad_sqnorm_sum(Tensor part, int64_t nparts, Tensor out) {
+  CHECK_CUDA(part);
+  CHECK_F32(part);
+  CHECK_F32(out);
+  TORCH_CHECK(nparts >= 0 && nparts <= part.numel() && out.numel() >= 1 &&
+                  out.device() == part.device(), "grad_sqnorm_sum: sizes");
+  const c10::OptionalDeviceGuard gd(device_of(part));
+  mpa::grad_sqnorm_sum(part.data_ptr<float>(), (int)nparts, out.data_ptr<float>(), cur_stream());
+}
+
+void hyper_update(Tensor step, Tensor hyper, Tensor part, int64_t nparts, int64_t kind,
+                  double base_lr, double warmup, double total, double min_ratio, double gamma,
+                  double decay_steps, double max_norm, double grad_scale) {
+  CHECK_CUDA(step);
+  CHECK_F32(step);
+  check_hyper(hyper, step);
+  CHECK_F32(part);
+  TORCH_CHECK(nparts >= 0 && nparts <= part.numel() && (nparts == 0 || part.device() == step.device()),
+              "hyper_update: nparts outside the workspace");
+  TORCH_CHECK(kind >= mpa::HYPER_CONSTANT && kind <= mpa::HYPER_STEP, "hyper_update: kind");
+  TORCH_CHECK(kind != mpa::HYPER_STEP || decay_steps > 0, "hyper_update: decay_steps > 0");
+  mpa::HyperCfg c;
+  c.kind = (int)kind;
+  c.base_lr = (float)base_lr;
+  c.warmup = (float)warmup;
+  c.total = (float)total;
+  c.min_ratio = (float)min_ratio;
+  c.gamma = (float)gamma;
+  c.decay_steps = (float)decay_steps;
+  c.max_norm = (float)max_norm;
+  c.grad_scale = (float)grad_scale;
+  const c10::OptionalDeviceGuard gd(device_of(step));
+  mpa::hyper_update(step.data_ptr<float>(), part.data_ptr<float>(), (int)nparts,
+                    hyper.data_ptr<float>(), c, cur_stream());
+}
+
+void adam_step_dev(Tensor p, Tensor g, Tensor m, Tensor v, Tensor shadow, Tensor step,
+                   Tensor hyper, double b1, double b2, double eps, double wd) {
+  CHECK_F32(p);
+  TORCH_CHECK(p.numel() % 4 == 0 && g.numel() >= p.numel() && m.numel() >= p.numel() &&
+                  v.numel() >= p.numel(), "adam_dev: sizes");
+  check_hyper(hyper, p);
+  const c10::OptionalDeviceGuard gd(device_of(p));
+  mpa::adam_step_dev(p.data_ptr<float>(), g.data_ptr<float>(), m.data_ptr<float>(),
+                     v.data_ptr<float>(), has(shadow) ? bpm(shadow) : nullptr,
+                     step.data_ptr<float>(), hyper.data_ptr<float>(), p.numel(), b1, b2, eps, wd,
+                     cur_stream());
+}
+
+void sgd_step_dev(Tensor p, Tensor g, Tensor buf, Tensor shadow, Tensor step, Tensor hyper,
+                  double momentum, double dampening, double wd, bool nesterov) {
+  CHECK_F32(p);
+  TORCH_CHECK(p.numel() % 4 == 0 && g.numel() >= p.numel() && buf.numel() >= p.numel(),
+              "sgd_dev: sizes");
+  check_hyper(hyper, p);
+  const c10::OptionalDeviceGuard gd(device_of(p));
+  mpa::sgd_step_dev(p.data_ptr<float>(), g.data_ptr<float>(), buf.data_ptr<float>(),
+                    has(shadow) ? bpm(shadow) : nullptr, step.data_ptr<float>(),
+                    hyper.data_ptr<float>(), p.numel(), momentum, dampening, wd,
+                    nesterov ? 1 : 0, cur_stream());
+}
+
 void transpose_krsc(Tensor w, Tensor wt, Tensor seg, int64_t total_tiles,
                     c10::optional<Tensor> step_inc) {
   CHECK_CUDA(w);
@@ -1812,6 +1895,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("argmax_correct", &argmax_correct);
   m.def("adam_step", &adam_step);
   m.def("sgd_step", &sgd_step);
+  m.def("grad_sqnorm", &grad_sqnorm,
+        "stage 1 of the arena's sum of squares: partials into the workspace; returns their count");
+  m.def("grad_sqnorm_sum", &grad_sqnorm_sum, "out[0] = fixed-order sum of the partials");
+  m.def("grad_sqnorm_grid_cap", []() { return (int64_t)mpa::grad_sqnorm_grid_cap(); });
+  m.def("grad_sqnorm_sweep", []() { return mpa::grad_sqnorm_sweep(); });
+  m.def("hyper_update", &hyper_update);
+  m.def("adam_step_dev", &adam_step_dev);
+  m.def("sgd_step_dev", &sgd_step_dev);
   m.def("cast_f32_bf16", &cast_f32_bf16);
   m.def("transpose_krsc", &transpose_krsc, py::arg("w"), py::arg("wt"), py::arg("seg"),
         py::arg("total_tiles"), py::arg("step_inc") = py::none());

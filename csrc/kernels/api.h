@@ -418,6 +418,40 @@ void sgd_step(float* p, const float* g, float* buf, bf16_raw* shadow, const floa
               int64_t n, float lr, float momentum, float dampening, float wd, int nesterov,
               float grad_scale, hipStream_t s);
 void cast_f32_bf16(const float* x, bf16_raw* y, int64_t n, hipStream_t s);
+// Per-step training recipe on the device (LR schedule + global-norm gradient clipping).
+// hyper[HYPER_N] fp32: the record hyper_update writes and the *_step_dev kernels read.
+enum { HYPER_LR = 0, HYPER_SCALE = 1, HYPER_NORM = 2, HYPER_COEF = 3, HYPER_SKIP = 4,
+       HYPER_NONFINITE = 5, HYPER_SUMSQ = 6, HYPER_N = 8 };
+enum { HYPER_CONSTANT = 0, HYPER_COSINE = 1, HYPER_STEP = 2 };
+struct HyperCfg {
+  int kind;           // HYPER_CONSTANT | HYPER_COSINE | HYPER_STEP
+  float base_lr;
+  float warmup;       // W: lr = base * (k + 1) / W while k < W
+  float total;        // T (cosine)
+  float min_ratio;    // r (cosine floor)
+  float gamma;        // step: base * gamma ^ floor(k / decay_steps)
+  float decay_steps;  // > 0 when kind == HYPER_STEP
+  float max_norm;     // clipping threshold (used when nparts > 0)
+  float grad_scale;   // the data-parallel 1/N
+};
+// sum of squares of g[0:n) (n % 4 == 0, 16-B aligned), stage 1: one partial per block into
+// part[0:returned count) (count <= grad_sqnorm_grid_cap()); fixed order, no atomics
+int grad_sqnorm(const float* g, int64_t n, float* part, hipStream_t s);
+int grad_sqnorm_grid_cap();
+int64_t grad_sqnorm_sweep();  // elements one full-grid round of stage 1 covers
+// stage 2 on its own: out[0] = fixed-order sum of part[0:nparts) (one block)
+void grad_sqnorm_sum(const float* part, int nparts, float* out, hipStream_t s);
+// stage 2 fused with the schedule / clip arithmetic: k = step[0]; nparts == 0: no clipping
+void hyper_update(const float* step, const float* part, int nparts, float* hyper,
+                  const HyperCfg& cfg, hipStream_t s);
+// adam_step / sgd_step with lr and the gradient scale read from hyper (no-op when
+// hyper[HYPER_SKIP] != 0)
+void adam_step_dev(float* p, const float* g, float* m, float* v, bf16_raw* shadow,
+                   const float* step, const float* hyper, int64_t n, float b1, float b2,
+                   float eps, float wd, hipStream_t s);
+void sgd_step_dev(float* p, const float* g, float* buf, bf16_raw* shadow, const float* step,
+                  const float* hyper, int64_t n, float momentum, float dampening, float wd,
+                  int nesterov, hipStream_t s);
 // wt[c][t][k] = w[k][t][c] per segment (src_off, dst_off, K, RS, C, first_tile) of seg
 // step_inc (optional): the optimizer's step counter, incremented by the same launch
 void transpose_krsc(const bf16_raw* w, bf16_raw* wt, const int64_t* seg, int nseg,

@@ -10,20 +10,27 @@
 
 namespace mpa {
 
-__global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const float* __restrict__ g,
-                                                    float* __restrict__ m, float* __restrict__ v,
-                                                    bf16_t* __restrict__ shadow,
-                                                    const float* __restrict__ step, int64_t n4,
-                                                    float lr, float b1, float b2, float eps,
-                                                    float wd, float gs) {
+// The update loops are __device__ functions shared by the host-argument kernels
+// (adam_kernel / sgd_kernel) and the device-argument kernels (adam_dev_kernel /
+// sgd_dev_kernel, which take lr and the gradient scale from the hyper record), so the two
+// forms cannot drift: with equal lr / scale they are bitwise equal.  The grid-stride
+// start and stride are taken in the kernels (GRID_I0 / GRID_STRIDE) and passed in: read in
+// a __device__ function, blockDim loses the kernel's uniform-workgroup-size fast path.
+#define GRID_I0 (blockIdx.x * (int64_t)blockDim.x + threadIdx.x)
+#define GRID_STRIDE ((int64_t)gridDim.x * blockDim.x)
+__device__ __forceinline__ void adam_body(float* __restrict__ p, const float* __restrict__ g,
+                                          float* __restrict__ m, float* __restrict__ v,
+                                          bf16_t* __restrict__ shadow,
+                                          const float* __restrict__ step, int64_t n4,
+                                          float lr, float b1, float b2, float eps,
+                                          float wd, float gs, int64_t i0, int64_t stride) {
   const float t = step[0] + 1.f;
   const float bc1 = 1.f - powf(b1, t);
   const float bc2s = sqrtf(1.f - powf(b2, t));
   const float step_size = lr / bc1;
   // streaming-bound: 1.33 GB per step at 44 M parameters in ~213 us (6.2 TB/s); the
   // correctly rounded sqrt / divide keep torch.optim.Adam's update bit-for-bit
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n4;
-       i += (int64_t)gridDim.x * blockDim.x) {
+  for (int64_t i = i0; i < n4; i += stride) {
     float4 pp = ((float4*)p)[i];
     const float4 gg = ((const float4*)g)[i];
     float4 mm = ((float4*)m)[i];
@@ -48,14 +55,36 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
   }
 }
 
-__global__ __launch_bounds__(256) void sgd_kernel(float* __restrict__ p, const float* __restrict__ g,
-                                                   float* __restrict__ buf, bf16_t* __restrict__ shadow,
-                                                   const float* __restrict__ step, int64_t n4,
-                                                   float lr, float momentum, float dampening,
-                                                   float wd, int nesterov, float gs) {
+__global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                    float* __restrict__ m, float* __restrict__ v,
+                                                    bf16_t* __restrict__ shadow,
+                                                    const float* __restrict__ step, int64_t n4,
+                                                    float lr, float b1, float b2, float eps,
+                                                    float wd, float gs) {
+  adam_body(p, g, m, v, shadow, step, n4, lr, b1, b2, eps, wd, gs, GRID_I0, GRID_STRIDE);
+}
+
+// lr / gradient scale / skip flag from the hyper record hyper_kernel wrote (stream order);
+// the skip branch is uniform over the whole grid
+__global__ __launch_bounds__(256) void adam_dev_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                        float* __restrict__ m, float* __restrict__ v,
+                                                        bf16_t* __restrict__ shadow,
+                                                        const float* __restrict__ step,
+                                                        const float* __restrict__ hyper, int64_t n4,
+                                                        float b1, float b2, float eps, float wd) {
+  if (hyper[HYPER_SKIP] != 0.f) return;
+  adam_body(p, g, m, v, shadow, step, n4, hyper[HYPER_LR], b1, b2, eps, wd, hyper[HYPER_SCALE],
+            GRID_I0, GRID_STRIDE);
+}
+
+__device__ __forceinline__ void sgd_body(float* __restrict__ p, const float* __restrict__ g,
+                                         float* __restrict__ buf, bf16_t* __restrict__ shadow,
+                                         const float* __restrict__ step, int64_t n4,
+                                         float lr, float momentum, float dampening,
+                                         float wd, int nesterov, float gs, int64_t i0,
+                                         int64_t stride) {
   const bool first = step[0] == 0.f;
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n4;
-       i += (int64_t)gridDim.x * blockDim.x) {
+  for (int64_t i = i0; i < n4; i += stride) {
     float4 pp = ((float4*)p)[i];
     const float4 gg = ((const float4*)g)[i];
     float4 bb = ((float4*)buf)[i];
@@ -76,6 +105,132 @@ __global__ __launch_bounds__(256) void sgd_kernel(float* __restrict__ p, const f
     if (momentum != 0.f) ((float4*)buf)[i] = bb;
     if (shadow) ((uint2*)shadow)[i] = make_uint2(pack2(pf[0], pf[1]), pack2(pf[2], pf[3]));
   }
+}
+
+__global__ __launch_bounds__(256) void sgd_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                   float* __restrict__ buf, bf16_t* __restrict__ shadow,
+                                                   const float* __restrict__ step, int64_t n4,
+                                                   float lr, float momentum, float dampening,
+                                                   float wd, int nesterov, float gs) {
+  sgd_body(p, g, buf, shadow, step, n4, lr, momentum, dampening, wd, nesterov, gs, GRID_I0,
+           GRID_STRIDE);
+}
+
+__global__ __launch_bounds__(256) void sgd_dev_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                       float* __restrict__ buf, bf16_t* __restrict__ shadow,
+                                                       const float* __restrict__ step,
+                                                       const float* __restrict__ hyper, int64_t n4,
+                                                       float momentum, float dampening, float wd,
+                                                       int nesterov) {
+  if (hyper[HYPER_SKIP] != 0.f) return;
+  sgd_body(p, g, buf, shadow, step, n4, hyper[HYPER_LR], momentum, dampening, wd, nesterov,
+           hyper[HYPER_SCALE], GRID_I0, GRID_STRIDE);
+}
+
+// ------------------------------------------------- global gradient norm + per-step recipe
+// grad_sqnorm: sum of squares of the flat fp32 gradient arena, for global-norm clipping.
+// A read-only stream: each thread issues SQ_LOADS 16-byte loads (a block covers a
+// contiguous 32 KB per round, lanes adjacent) before it consumes any, squares into four
+// accumulators in a fixed order, then wave64 shuffle -> LDS -> one float per block in the
+// workspace slab.  No float atomics: hyper_kernel (one block) sums the slab in a fixed
+// order, so the result depends only on (values, n) - bitwise reproducible in every mode
+// and equal on every data-parallel rank after the all-reduce.
+// The arena's alignment padding (parallel/arena.py ALIGN = 64) is part of the sum: it is
+// zero after zero_grad and no kernel writes it, and it must stay zero
+// (tests/test_recipe_gpu.py asserts it after a training step).
+constexpr int SQ_LOADS = 8;       // 16-byte loads in flight per thread (the slab reductions' 8)
+constexpr int SQ_GRID_CAP = 2048;  // 256 CUs x 8 blocks, a multiple of the 8 XCDs
+
+__global__ __launch_bounds__(256) void grad_sqnorm_kernel(const float4* __restrict__ g, int64_t n4,
+                                                          float* __restrict__ part) {
+  float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
+  const int64_t round = (int64_t)gridDim.x * (256 * SQ_LOADS);
+  for (int64_t base = (int64_t)blockIdx.x * (256 * SQ_LOADS); base < n4; base += round) {
+    float4 x[SQ_LOADS];
+    if (base + 256 * SQ_LOADS <= n4) {  // (uniform per block)
+#pragma unroll
+      for (int u = 0; u < SQ_LOADS; ++u) x[u] = g[base + u * 256 + threadIdx.x];
+    } else {
+#pragma unroll
+      for (int u = 0; u < SQ_LOADS; ++u) {
+        const int64_t i = base + u * 256 + threadIdx.x;
+        x[u] = i < n4 ? g[i] : make_float4(0.f, 0.f, 0.f, 0.f);
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < SQ_LOADS; ++u) {
+      a0 += x[u].x * x[u].x;
+      a1 += x[u].y * x[u].y;
+      a2 += x[u].z * x[u].z;
+      a3 += x[u].w * x[u].w;
+    }
+  }
+  __shared__ float ws[4];
+  const float w = wave_sum((a0 + a1) + (a2 + a3));
+  if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = w;
+  __syncthreads();
+  if (threadIdx.x == 0) part[blockIdx.x] = (ws[0] + ws[1]) + (ws[2] + ws[3]);
+}
+
+// fixed-order sum of the slab by ONE block of 256 threads; the result is valid in thread 0
+__device__ __forceinline__ float slab_sum(const float* __restrict__ part, int nparts) {
+  __shared__ float ws[4];
+  float a = 0.f;
+  for (int i = threadIdx.x; i < nparts; i += 256) a += part[i];
+  a = wave_sum(a);
+  if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = a;
+  __syncthreads();
+  return (ws[0] + ws[1]) + (ws[2] + ws[3]);
+}
+
+__global__ __launch_bounds__(256) void sqnorm_sum_kernel(const float* __restrict__ part, int nparts,
+                                                         float* __restrict__ out) {
+  const float s = slab_sum(part, nparts);
+  if (threadIdx.x == 0) out[0] = s;
+}
+
+// hyper_update: this step's learning rate (warm-up, then constant | cosine | step decay of
+// the 0-based update index k = step[0]) and, with clipping (nparts > 0), the global norm of
+// the averaged gradient, torch's clip coefficient and the non-finite skip flag.  One block;
+// thread 0 writes the record with ordinary stores.
+__global__ __launch_bounds__(256) void hyper_kernel(const float* __restrict__ step,
+                                                    const float* __restrict__ part, int nparts,
+                                                    float* __restrict__ hyper, HyperCfg c) {
+  float sumsq = 0.f;
+  if (nparts > 0) sumsq = slab_sum(part, nparts);
+  if (threadIdx.x != 0) return;
+  const float k = step[0];
+  float lr = c.base_lr;
+  if (k < c.warmup) {
+    lr = c.base_lr * (k + 1.f) / c.warmup;
+  } else if (c.kind == HYPER_COSINE) {
+    if (k < c.total) {
+      const float p = (k - c.warmup) / fmaxf(1.f, c.total - c.warmup);
+      lr = c.base_lr * (c.min_ratio + (1.f - c.min_ratio) * 0.5f * (1.f + cospif(p)));
+    } else {
+      lr = c.base_lr * c.min_ratio;
+    }
+  } else if (c.kind == HYPER_STEP) {
+    lr = c.base_lr * powf(c.gamma, floorf(k / c.decay_steps));
+  }
+  float norm = 0.f, coef = 1.f, skip = 0.f, bad = hyper[HYPER_NONFINITE];
+  if (nparts > 0) {
+    norm = c.grad_scale * sqrtf(sumsq);
+    if (!isfinite(sumsq)) {  // inf / NaN gradients (or a sum past fp32): skip the update
+      skip = 1.f;
+      coef = 0.f;
+      bad += 1.f;
+    } else if (norm > c.max_norm) {
+      coef = fminf(1.f, c.max_norm / (norm + 1e-6f));  // torch.nn.utils.clip_grad_norm_
+    }
+  }
+  hyper[HYPER_LR] = lr;
+  hyper[HYPER_SCALE] = c.grad_scale * coef;  // coef == 1: bitwise grad_scale
+  hyper[HYPER_NORM] = norm;
+  hyper[HYPER_COEF] = coef;
+  hyper[HYPER_SKIP] = skip;
+  hyper[HYPER_NONFINITE] = bad;
+  hyper[HYPER_SUMSQ] = sumsq;
 }
 
 __global__ void cast_kernel(const float* __restrict__ x, bf16_t* __restrict__ y, int64_t n4) {
@@ -104,6 +259,43 @@ void sgd_step(float* p, const float* g, float* buf, bf16_raw* shadow, const floa
   const int64_t n4 = n / 4;
   hipLaunchKernelGGL(sgd_kernel, dim3(blocks_for(n4)), dim3(256), 0, s, p, g, buf, shadow, step,
                      n4, lr, momentum, dampening, wd, nesterov, gs);
+}
+
+void adam_step_dev(float* p, const float* g, float* m, float* v, bf16_raw* shadow,
+                   const float* step, const float* hyper, int64_t n, float b1, float b2,
+                   float eps, float wd, hipStream_t s) {
+  const int64_t n4 = n / 4;
+  hipLaunchKernelGGL(adam_dev_kernel, dim3(blocks_for(n4)), dim3(256), 0, s, p, g, m, v, shadow,
+                     step, hyper, n4, b1, b2, eps, wd);
+}
+
+void sgd_step_dev(float* p, const float* g, float* buf, bf16_raw* shadow, const float* step,
+                  const float* hyper, int64_t n, float momentum, float dampening, float wd,
+                  int nesterov, hipStream_t s) {
+  const int64_t n4 = n / 4;
+  hipLaunchKernelGGL(sgd_dev_kernel, dim3(blocks_for(n4)), dim3(256), 0, s, p, g, buf, shadow,
+                     step, hyper, n4, momentum, dampening, wd, nesterov);
+}
+
+int grad_sqnorm_grid_cap() { return SQ_GRID_CAP; }
+int64_t grad_sqnorm_sweep() { return (int64_t)SQ_GRID_CAP * 256 * SQ_LOADS * 4; }
+
+int grad_sqnorm(const float* g, int64_t n, float* part, hipStream_t s) {
+  const int64_t n4 = n / 4, per = 256 * SQ_LOADS;
+  int64_t blocks = std::max<int64_t>(1, std::min<int64_t>((n4 + per - 1) / per, SQ_GRID_CAP));
+  blocks = (blocks + 7) / 8 * 8;  // a multiple of the XCD count (<= SQ_GRID_CAP, itself one)
+  hipLaunchKernelGGL(grad_sqnorm_kernel, dim3((int)blocks), dim3(256), 0, s, (const float4*)g, n4,
+                     part);
+  return (int)blocks;
+}
+
+void grad_sqnorm_sum(const float* part, int nparts, float* out, hipStream_t s) {
+  hipLaunchKernelGGL(sqnorm_sum_kernel, dim3(1), dim3(256), 0, s, part, nparts, out);
+}
+
+void hyper_update(const float* step, const float* part, int nparts, float* hyper,
+                  const HyperCfg& cfg, hipStream_t s) {
+  hipLaunchKernelGGL(hyper_kernel, dim3(1), dim3(256), 0, s, step, part, nparts, hyper, cfg);
 }
 
 void cast_f32_bf16(const float* x, bf16_raw* y, int64_t n, hipStream_t s) {

@@ -63,6 +63,13 @@ class Config:
     optimizer: str = "adam"                # adam | sgd
     momentum: float = 0.9
     weight_decay: float = 0.0
+    # training recipe on the device (optim.py; all off by default = the reference's recipe)
+    lr_schedule: str = "constant"          # constant | cosine | step (after the warm-up)
+    warmup_steps: int = 0                  # linear warm-up: lr * (k + 1) / warmup_steps
+    lr_min_ratio: float = 0.0              # cosine floor, as a fraction of LR
+    lr_gamma: float = 0.1                  # step: LR * lr_gamma ^ floor(k / lr_decay_steps)
+    lr_decay_steps: int = 0
+    clip_grad_norm: float = 0.0            # global-norm gradient clipping (0.0 = off)
     bucket_mb: float = 16.0                # gradient all-reduce bucket size (MiB)
     grad_comm_dtype: str = "fp32"          # fp32 | bf16 (wire dtype of the gradient all-reduce)
     overlap_comm: bool = True              # launch bucket all-reduce during backward
@@ -96,8 +103,24 @@ class Config:
                 self.MODEL_NAME, MODEL_NAMES))
         if self.optimizer not in ("adam", "sgd"):
             raise ValueError("optimizer must be adam|sgd")
+        if self.lr_schedule not in ("constant", "cosine", "step"):
+            raise ValueError("lr_schedule must be constant|cosine|step")
+        if self.warmup_steps < 0 or self.lr_decay_steps < 0:
+            raise ValueError("warmup_steps and lr_decay_steps must be >= 0")
+        if not 0.0 <= self.lr_min_ratio <= 1.0:
+            raise ValueError("lr_min_ratio must be in [0, 1]")
+        if self.lr_schedule == "step" and (self.lr_decay_steps <= 0 or self.lr_gamma <= 0.0):
+            raise ValueError("lr_schedule=step needs lr_decay_steps > 0 and lr_gamma > 0")
+        if not self.clip_grad_norm >= 0.0:
+            raise ValueError("clip_grad_norm must be >= 0 (0 = off)")
 
     # -----------------------------------------------------------------------------------
+    @property
+    def recipe_on(self) -> bool:
+        """True when a schedule, a warm-up or gradient clipping is configured."""
+        return (self.lr_schedule != "constant" or self.warmup_steps > 0
+                or self.clip_grad_norm > 0.0)
+
     @property
     def input_hw(self):
         if self.image_size:

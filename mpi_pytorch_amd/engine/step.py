@@ -255,6 +255,10 @@ class TrainStep:
             m.range_pop()
             m.range_push("comm_wait")
         self.bucketer.finish()
+        # (the recipe's gradient norm, inside opt.step(), reads the whole gradient arena:
+        # the side weight-gradient stream was joined in the finally above, and finish() made
+        # this stream wait for every bucket's all-reduce, so it sees the final summed
+        # gradients - identical on every rank; grad_scale turns their norm into the average's)
         if t is not None:
             t.mark(3)
         if m is not None:
@@ -376,11 +380,18 @@ def reserve_device_memory(device, gib: float) -> float:
 def build_training(name: str, num_classes: int, device, world: World, lr: float,
                    optimizer: str = "adam", momentum: float = 0.9, weight_decay: float = 0.0,
                    feature_extract: bool = False, bucket_mb: float = 16.0, overlap: bool = True,
-                   comm_dtype: str = "fp32", comm_ctas: Optional[int] = None):
+                   comm_dtype: str = "fp32", comm_ctas: Optional[int] = None,
+                   schedule: Optional[dict] = None, clip_grad_norm: float = 0.0):
+    """``schedule``: keyword arguments of ``optim.set_schedule`` (None: constant LR);
+    ``clip_grad_norm`` > 0: global-norm gradient clipping (``optim.set_clip``)."""
     model, input_size = build_model(name, num_classes, feature_extract, device, world,
                                     bucket_mb=bucket_mb, overlap=overlap, comm_dtype=comm_dtype,
                                     comm_ctas=comm_ctas)
     opt = build_optimizer(optimizer, model, lr, momentum, weight_decay)
+    if schedule is not None:
+        opt.set_schedule(**schedule)
+    if clip_grad_norm > 0.0:
+        opt.set_clip(clip_grad_norm)
     sync_params(model)
     model.train()
     return model, opt, TrainStep(model, opt, world), input_size

@@ -182,10 +182,19 @@ def run_training(cfg: Config) -> dict:
         from .step import reserve_device_memory
         log.debug("reserved {} GiB of device memory".format(
             reserve_device_memory(dev, cfg.reserve_gib)))
+    schedule = None
+    if cfg.lr_schedule != "constant" or cfg.warmup_steps > 0:
+        # the schedule runs on the device step counter, which a checkpoint restores: a
+        # resumed run continues it from the saved step
+        schedule = dict(kind=cfg.lr_schedule, warmup_steps=cfg.warmup_steps,
+                        total_steps=cfg.NUM_EPOCHS * steps_per_epoch,
+                        lr_min_ratio=cfg.lr_min_ratio, gamma=cfg.lr_gamma,
+                        decay_steps=cfg.lr_decay_steps)
     model, opt, step, _input_size = build_training(
         cfg.MODEL_NAME, cfg.NUM_CLASSES, dev, world, cfg.LR, cfg.optimizer, cfg.momentum,
         cfg.weight_decay, cfg.FEATURE_EXTRACT, cfg.bucket_mb, cfg.overlap_comm,
-        cfg.grad_comm_dtype, None if cfg.grad_comm_ctas < 0 else cfg.grad_comm_ctas)
+        cfg.grad_comm_dtype, None if cfg.grad_comm_ctas < 0 else cfg.grad_comm_ctas,
+        schedule=schedule, clip_grad_norm=cfg.clip_grad_norm)
     log.info("_Model Created: {}".format(cfg.MODEL_NAME))
     spec = input_spec(model, out_hw)
     for ld in (train_loader, val_loader):
@@ -247,6 +256,10 @@ def run_training(cfg: Config) -> dict:
         rec = {"epoch": epoch, "train_loss": tr_loss, "time_s": dt,
                "img_per_s_rank": nimg / dt if dt > 0 else 0.0,
                "img_per_s_global": nimg * size / dt if dt > 0 else 0.0}
+        if opt.recipe_on:  # one sync each, at the epoch end
+            rec["lr"] = opt.current_lr()
+            rec["grad_norm"] = opt.last_grad_norm() if cfg.clip_grad_norm > 0.0 else None
+            rec["nonfinite_steps"] = opt.nonfinite_steps()
         if step.timer is not None:
             rec["phases_ms"] = step.timer.summary()
         if size > 1:

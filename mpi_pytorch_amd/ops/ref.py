@@ -18,6 +18,7 @@ from __future__ import annotations
 import math
 from typing import Optional, Tuple
 
+import numpy as np
 import torch
 import torch.nn.functional as F
 
@@ -613,6 +614,77 @@ def sgd_step(master, grad, buf, shadow, step_t, lr, momentum, dampening, wd, nes
     master.add_(g, alpha=-lr)
     if _opt(shadow) is not None:
         shadow.copy_(master)
+
+
+# ---- per-step recipe (LR schedule + global-norm clipping); csrc/kernels/optim.hip
+# hyper record slots (csrc/kernels/api.h HYPER_*)
+HYPER_LR, HYPER_SCALE, HYPER_NORM, HYPER_COEF, HYPER_SKIP, HYPER_NONFINITE, HYPER_SUMSQ = range(7)
+HYPER_N = 8
+SCHEDULE_KINDS = ("constant", "cosine", "step")
+
+
+def grad_sqnorm_grid_cap():
+    return 1
+
+
+def grad_sqnorm(grad, part):
+    """Sum of squares of the gradient arena, accumulated in float64; one partial."""
+    part[0] = float(grad.double().pow(2).sum())
+    return 1
+
+
+def grad_sqnorm_sum(part, nparts, out):
+    out[0] = float(part[:nparts].double().sum())
+
+
+def hyper_update(step_t, hyper, part, nparts, kind, base_lr, warmup, total, min_ratio, gamma,
+                 decay_steps, max_norm, grad_scale):
+    """fp32 mirror of hyper_kernel: k = step_t (the 0-based index of this update)."""
+    f = np.float32
+    k, base, W, T, r = f(float(step_t.item())), f(base_lr), f(warmup), f(total), f(min_ratio)
+    lr = base
+    if k < W:
+        lr = base * (k + f(1)) / W
+    elif kind == 1:
+        if k < T:
+            p = (k - W) / max(f(1), T - W)
+            lr = base * (r + (f(1) - r) * f(0.5) * (f(1) + f(math.cos(math.pi * float(p)))))
+        else:
+            lr = base * r
+    elif kind == 2:
+        lr = base * f(float(gamma) ** math.floor(float(k / f(decay_steps))))
+    gs = f(grad_scale)
+    norm, coef, skip, bad = f(0), f(1), f(0), f(float(hyper[HYPER_NONFINITE]))
+    sumsq = f(0)
+    if nparts > 0:
+        with np.errstate(over="ignore", invalid="ignore"):
+            sumsq = f(float(part[:nparts].double().sum()))
+            norm = gs * np.sqrt(sumsq)
+        if not np.isfinite(sumsq):
+            skip, coef, bad = f(1), f(0), bad + f(1)
+        elif norm > f(max_norm):
+            coef = min(f(1), f(max_norm) / (norm + f(1e-6)))
+    hyper[HYPER_LR] = float(lr)
+    hyper[HYPER_SCALE] = float(gs * coef)
+    hyper[HYPER_NORM] = float(norm)
+    hyper[HYPER_COEF] = float(coef)
+    hyper[HYPER_SKIP] = float(skip)
+    hyper[HYPER_NONFINITE] = float(bad)
+    hyper[HYPER_SUMSQ] = float(sumsq)
+
+
+def adam_step_dev(master, grad, m, v, shadow, step_t, hyper, b1, b2, eps, wd):
+    if float(hyper[HYPER_SKIP]) != 0.0:
+        return
+    adam_step(master, grad, m, v, shadow, step_t, float(hyper[HYPER_LR]), b1, b2, eps, wd,
+              float(hyper[HYPER_SCALE]))
+
+
+def sgd_step_dev(master, grad, buf, shadow, step_t, hyper, momentum, dampening, wd, nesterov):
+    if float(hyper[HYPER_SKIP]) != 0.0:
+        return
+    sgd_step(master, grad, buf, shadow, step_t, float(hyper[HYPER_LR]), momentum, dampening, wd,
+             nesterov, float(hyper[HYPER_SCALE]))
 
 
 # ------------------------------------------------------------------------ preprocessing

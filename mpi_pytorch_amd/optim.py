@@ -13,16 +13,60 @@ format exactly (per-parameter ``exp_avg``/``exp_avg_sq``/``step`` or ``momentum_
 in the torchvision layout, ``param_groups`` with ``params`` = indices into
 ``model.parameters()``), so checkpoints round-trip with the reference's
 ``helpers.load_checkpoint`` (``helpers.py:10-15``).
+
+Training recipe (beyond the reference, off by default): ``set_schedule`` / ``set_clip``
+turn on a per-step learning-rate schedule and global-norm gradient clipping that are
+computed on the device from the device step counter, so they cost no host sync and stay
+correct under HIP-graph replay.  ``step()`` then runs ``grad_sqnorm`` (only with clipping)
+-> ``hyper_update`` -> ``adam_step_dev`` / ``sgd_step_dev``; with the recipe off it
+launches exactly the kernels it always did.  With ``k`` the 0-based index of the update
+(``step_t`` before it), ``W`` warm-up steps, ``T`` total steps and ``r = lr_min_ratio``:
+
+* ``k < W``:  ``lr = base * (k + 1) / W``;
+* constant:   ``lr = base``;
+* cosine:     ``lr = base * (r + (1 - r) * 0.5 * (1 + cos(pi * (k - W) / max(1, T - W))))``
+  for ``k < T`` and ``base * r`` from ``T`` on;
+* step:       ``lr = base * gamma ** floor(k / decay_steps)``.
+
+Clipping is ``torch.nn.utils.clip_grad_norm_`` on the averaged gradient: ``total =
+grad_scale * sqrt(sum g^2)`` over the trainable arena, ``coef = min(1, max_norm / (total +
+1e-6))`` (exactly 1 when ``total <= max_norm``), and the optimizer scales gradients by
+``grad_scale * coef`` before weight decay.  While clipping is on, a step whose ``sum g^2``
+is inf / NaN is skipped - weights, moments and bf16 shadow stay bitwise unchanged and the
+device counter ``nonfinite_steps`` goes up - but ``step_t`` still advances: a skipped step
+counts for the schedule and for Adam's bias correction.
 """
 from __future__ import annotations
 
-from typing import Dict, List
+from typing import Dict, List, Optional
 
 import torch
 import torch.nn as nn
 
 from .ops import functional as Fn
+from .ops import ref as _ref
 from .parallel.arena import ParamArena
+
+SCHEDULE_KINDS = _ref.SCHEDULE_KINDS
+
+
+def scheduled_lr(base: float, k: int, kind: str = "constant", warmup_steps: int = 0,
+                 total_steps: int = 0, lr_min_ratio: float = 0.0, gamma: float = 0.1,
+                 decay_steps: int = 0) -> float:
+    """The schedule in host float64 (the module docstring's formulas) for update index
+    ``k``: what the device record holds to fp32 rounding.  For logs and tests."""
+    import math
+    W, T, r = warmup_steps, total_steps, lr_min_ratio
+    if k < W:
+        return base * (k + 1) / W
+    if kind == "cosine":
+        if k >= T:
+            return base * r
+        p = (k - W) / max(1, T - W)
+        return base * (r + (1 - r) * 0.5 * (1 + math.cos(math.pi * p)))
+    if kind == "step":
+        return base * gamma ** (k // decay_steps)
+    return base
 
 
 def _export(p, t):
@@ -44,6 +88,14 @@ class _FlatOptimizer:
         dev = arena.device
         self.step_t = torch.zeros(1, dtype=torch.float32, device=dev)
         self.grad_scale = 1.0
+        # the recipe's device record (ops/ref.py HYPER_*: lr, effective grad scale, grad
+        # norm, clip coefficient, skip flag, non-finite step count, sum of squares) and the
+        # norm's per-block workspace: tensor attributes, so TrainStep snapshots / restores
+        # them around graph capture with the rest of the optimizer state
+        self.hyper = None
+        self.norm_ws = None
+        self._schedule: Optional[Dict] = None
+        self._max_norm = 0.0
         self.param_groups = [self._group_defaults()]
         self.param_groups[0]["params"] = self.params
 
@@ -65,6 +117,95 @@ class _FlatOptimizer:
     def _update(self, lo: int, hi: int) -> None:
         raise NotImplementedError
 
+    def _update_dev(self, lo: int, hi: int) -> None:
+        raise NotImplementedError
+
+    # training recipe -----------------------------------------------------------------
+    @property
+    def recipe_on(self) -> bool:
+        return self._schedule is not None or self._max_norm > 0.0
+
+    def _ensure_record(self) -> None:
+        if self.hyper is None:
+            dev = self.arena.device
+            k = self._kernel()
+            self.hyper = torch.zeros(_ref.HYPER_N, dtype=torch.float32, device=dev)
+            self.hyper[_ref.HYPER_LR] = float(self.lr)
+            self.hyper[_ref.HYPER_SCALE] = float(self.grad_scale)
+            self.hyper[_ref.HYPER_COEF] = 1.0
+            self.norm_ws = torch.zeros(int(k.grad_sqnorm_grid_cap()), dtype=torch.float32,
+                                       device=dev)
+
+    def set_schedule(self, kind: str = "constant", warmup_steps: int = 0, total_steps: int = 0,
+                     lr_min_ratio: float = 0.0, gamma: float = 0.1, decay_steps: int = 0) -> None:
+        """Per-step learning-rate schedule computed on the device (module docstring).
+        Set it before a step is captured into a HIP graph: the schedule's constants are
+        kernel arguments, only the step counter and the gradients are read per replay."""
+        if kind not in SCHEDULE_KINDS:
+            raise ValueError("schedule must be one of {}".format("|".join(SCHEDULE_KINDS)))
+        if warmup_steps < 0 or total_steps < 0 or decay_steps < 0:
+            raise ValueError("warmup_steps, total_steps and decay_steps must be >= 0")
+        if not 0.0 <= lr_min_ratio <= 1.0:
+            raise ValueError("lr_min_ratio must be in [0, 1]")
+        if kind == "step" and (decay_steps <= 0 or gamma <= 0.0):
+            raise ValueError("the step schedule needs decay_steps > 0 and gamma > 0")
+        if kind == "cosine" and total_steps <= warmup_steps:
+            raise ValueError("the cosine schedule needs total_steps > warmup_steps")
+        self._schedule = dict(kind=str(kind), warmup_steps=int(warmup_steps),
+                              total_steps=int(total_steps), lr_min_ratio=float(lr_min_ratio),
+                              gamma=float(gamma), decay_steps=int(decay_steps))
+        self._ensure_record()
+
+    def set_clip(self, max_norm: float) -> None:
+        """Clip the global norm of the averaged gradient to ``max_norm`` (0 turns it off)."""
+        if max_norm < 0 or max_norm != max_norm:
+            raise ValueError("max_norm must be >= 0")
+        self._max_norm = float(max_norm)
+        if self._max_norm > 0:
+            self._ensure_record()
+
+    def _recipe_step(self) -> None:
+        """norm (only with clipping) -> hyper record -> device-argument update."""
+        n = self.arena.n_train
+        k = self._kernel()
+        nparts = 0
+        if self._max_norm > 0.0:
+            nparts = int(k.grad_sqnorm(self.arena.grad[:n], self.norm_ws))
+        sc = self._schedule or dict(kind="constant", warmup_steps=0, total_steps=0,
+                                    lr_min_ratio=0.0, gamma=0.1, decay_steps=0)
+        k.hyper_update(self.step_t, self.hyper, self.norm_ws, nparts,
+                       SCHEDULE_KINDS.index(sc["kind"]), float(self.lr),
+                       float(sc["warmup_steps"]), float(sc["total_steps"]),
+                       float(sc["lr_min_ratio"]), float(sc["gamma"]), float(sc["decay_steps"]),
+                       float(self._max_norm), float(self.grad_scale))
+        self._update_dev(0, n)
+
+    def step(self) -> None:
+        if self.arena.n_train == 0:
+            return
+        if self.recipe_on:
+            self._recipe_step()
+        else:
+            self._update(0, self.arena.n_train)
+        self.arena.refresh_transposed(step_inc=self.step_t)
+
+    def _read(self, slot: int) -> float:
+        if self.hyper is None:
+            raise RuntimeError("no schedule or clipping is set on this optimizer")
+        return float(self.hyper[slot].item())
+
+    def current_lr(self) -> float:
+        """The learning rate the last update used (the base LR before any; one host sync)."""
+        return self._read(_ref.HYPER_LR) if self.hyper is not None else float(self.lr)
+
+    def last_grad_norm(self) -> float:
+        """Global norm of the last step's averaged gradient, before clipping (one sync)."""
+        return self._read(_ref.HYPER_NORM)
+
+    def nonfinite_steps(self) -> int:
+        """Updates skipped so far for inf / NaN gradients (one sync)."""
+        return int(self._read(_ref.HYPER_NONFINITE))
+
     def _kernel(self):
         return Fn.K(self.arena.master)
 
@@ -82,13 +223,29 @@ class _FlatOptimizer:
             state[i] = self._param_state(p, o, e, torch_step)
         g = {k: v for k, v in self.param_groups[0].items() if k != "params"}
         g["params"] = list(range(len(self.params)))
+        g["mpa_step"] = torch_step
+        if self.recipe_on:  # plain Python types only (weights_only=True loading)
+            g["initial_lr"] = float(self.lr)
+            g["lr"] = self.current_lr()  # the last scheduled value, as torch schedulers leave it
+            g["mpa_schedule"] = dict(self._schedule) if self._schedule is not None else None
+            g["mpa_clip_grad_norm"] = float(self._max_norm)
+            g["mpa_nonfinite_steps"] = self.nonfinite_steps()
         return {"state": state, "param_groups": [g]}
 
     def load_state_dict(self, sd: Dict) -> None:
         g = sd["param_groups"][0]
         for k, v in g.items():
-            if k != "params":
+            if k != "params" and not k.startswith("mpa_") and k != "initial_lr":
                 self.param_groups[0][k] = v
+        if "initial_lr" in g:  # a recipe checkpoint's "lr" is the last scheduled value
+            self.param_groups[0]["lr"] = float(g["initial_lr"])
+        if g.get("mpa_schedule") is not None:
+            self.set_schedule(**g["mpa_schedule"])
+        if g.get("mpa_clip_grad_norm", 0.0) > 0.0:
+            self.set_clip(g["mpa_clip_grad_norm"])
+        if self.hyper is not None:
+            self.hyper[_ref.HYPER_LR] = float(g.get("lr", self.lr))
+            self.hyper[_ref.HYPER_NONFINITE] = float(g.get("mpa_nonfinite_steps", 0))
         steps = []
         for i, st in sd["state"].items():
             p = self.params[int(i)]
@@ -96,7 +253,9 @@ class _FlatOptimizer:
                 continue
             o, e = self.arena.slice_of(p)
             steps.append(self._load_param_state(p, o, e, st))
-        if steps:
+        if "mpa_step" in g:  # (SGD's per-parameter state carries no step)
+            self.step_t.fill_(float(g["mpa_step"]))
+        elif steps:
             self.step_t.fill_(max(steps))
 
 
@@ -127,11 +286,15 @@ class FusedAdam(_FlatOptimizer):
                                  float(g["lr"]), float(b1), float(b2), float(g["eps"]),
                                  float(g["weight_decay"]), float(self.grad_scale))
 
-    def step(self) -> None:
-        if self.arena.n_train == 0:
-            return
-        self._update(0, self.arena.n_train)
-        self.arena.refresh_transposed(step_inc=self.step_t)
+    def _update_dev(self, lo: int, hi: int) -> None:
+        g = self.param_groups[0]
+        b1, b2 = g["betas"]
+        sh = self._shadow()
+        self._kernel().adam_step_dev(self.arena.master[lo:hi], self.arena.grad[lo:hi],
+                                     self.exp_avg[lo:hi], self.exp_avg_sq[lo:hi],
+                                     sh[lo:hi] if sh.numel() else sh, self.step_t, self.hyper,
+                                     float(b1), float(b2), float(g["eps"]),
+                                     float(g["weight_decay"]))
 
     def _param_state(self, p, o, e, step):
         return {"step": torch.tensor(step),
@@ -170,11 +333,14 @@ class FusedSGD(_FlatOptimizer):
                                 float(g["dampening"]), float(g["weight_decay"]),
                                 bool(g["nesterov"]), float(self.grad_scale))
 
-    def step(self) -> None:
-        if self.arena.n_train == 0:
-            return
-        self._update(0, self.arena.n_train)
-        self.arena.refresh_transposed(step_inc=self.step_t)
+    def _update_dev(self, lo: int, hi: int) -> None:
+        g = self.param_groups[0]
+        sh = self._shadow()
+        self._kernel().sgd_step_dev(self.arena.master[lo:hi], self.arena.grad[lo:hi],
+                                    self.momentum_buffer[lo:hi],
+                                    sh[lo:hi] if sh.numel() else sh, self.step_t, self.hyper,
+                                    float(g["momentum"]), float(g["dampening"]),
+                                    float(g["weight_decay"]), bool(g["nesterov"]))
 
     def _param_state(self, p, o, e, step):
         return {"momentum_buffer":

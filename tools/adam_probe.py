@@ -2,14 +2,38 @@
 at ResNet-18 / ResNet-50-ish / VGG-16 parameter counts, and report achieved HBM bandwidth
 (30 bytes per parameter: fp32 master/m/v read+write, fp32 grad read, bf16 shadow write).
 
-    python tools/adam_probe.py
+With ``--recipe`` also the training recipe's kernels at the same sizes: ``adam_step_dev``
+(Adam with lr / gradient scale read from the device record; same traffic) interleaved with
+``adam_step``, and the gradient-norm pass ``grad_sqnorm`` + ``hyper_update`` (4 bytes per
+parameter, read only).
+
+    python tools/adam_probe.py [--recipe]
 """
+import sys
+
 import torch
 
 from mpi_pytorch_amd.ops import _ext
 
 
+def _time(fn, flush, cold, iters=12):
+    ts = []
+    for it in range(iters):
+        if cold:
+            flush.fill_(float(it))
+        e0, e1 = torch.cuda.Event(True), torch.cuda.Event(True)
+        e0.record()
+        fn()
+        e1.record()
+        torch.cuda.synchronize()
+        if it >= 2:
+            ts.append(e0.elapsed_time(e1) * 1e3)
+    ts.sort()
+    return ts[len(ts) // 2], ts[0], ts[-1]
+
+
 def main():
+    recipe = "--recipe" in sys.argv[1:]
     k = _ext.load()
     dev = torch.device("cuda:0")
     flush = torch.empty(1 << 30, dtype=torch.float32, device=dev)
@@ -21,22 +45,33 @@ def main():
         v = torch.zeros(n, device=dev)
         sh = torch.empty(n, dtype=torch.bfloat16, device=dev)
         st = torch.zeros(1, device=dev)
+        hyper = torch.zeros(8, device=dev)
+        hyper[0], hyper[1] = 1e-3, 1.0
+        ws = torch.zeros(k.grad_sqnorm_grid_cap(), device=dev)
+
+        def adam():
+            k.adam_step(p, g, m, v, sh, st, 1e-3, 0.9, 0.999, 1e-8, 0.0, 1.0)
+
+        def adam_dev():
+            k.adam_step_dev(p, g, m, v, sh, st, hyper, 0.9, 0.999, 1e-8, 0.0)
+
+        def norm():  # both launches of a clipped step: partials, then sum + hyper record
+            parts = k.grad_sqnorm(g, ws)
+            k.hyper_update(st, hyper, ws, parts, 0, 1e-3, 0.0, 0.0, 0.0, 0.1, 0.0, 1e30, 1.0)
+
+        def norm1():  # the streaming pass alone
+            k.grad_sqnorm(g, ws)
+
+        runs = [("adam", adam, 30)]
+        if recipe:
+            # (adam / adam_dev alternate twice: the spread between equal runs is the yardstick)
+            runs += [("adam_dev", adam_dev, 30), ("adam", adam, 30), ("adam_dev", adam_dev, 30),
+                     ("sqnorm", norm1, 4), ("sqnorm+hyper", norm, 4)]
         for cold in (False, True):
-            ts = []
-            for it in range(12):
-                if cold:
-                    flush.fill_(float(it))
-                e0, e1 = torch.cuda.Event(True), torch.cuda.Event(True)
-                e0.record()
-                k.adam_step(p, g, m, v, sh, st, 1e-3, 0.9, 0.999, 1e-8, 0.0, 1.0)
-                e1.record()
-                torch.cuda.synchronize()
-                if it >= 2:
-                    ts.append(e0.elapsed_time(e1) * 1e3)
-            ts.sort()
-            us = ts[len(ts) // 2]
-            print(f"adam n={n / 1e6:7.2f}M {'cold' if cold else 'warm'}: {us:8.1f} us  "
-                  f"{30 * n / us / 1e6:6.2f} TB/s", flush=True)
+            for name, fn, bpp in runs:
+                us, lo, hi = _time(fn, flush, cold)
+                print(f"{name:13s} n={n / 1e6:7.2f}M {'cold' if cold else 'warm'}: {us:8.1f} us "
+                      f"(min {lo:.1f}, max {hi:.1f})  {bpp * n / us / 1e6:6.2f} TB/s", flush=True)
         del p, g, m, v, sh
 
 

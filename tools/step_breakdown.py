@@ -12,7 +12,8 @@ from collections import defaultdict
 
 CATS = [
     ("aten/runtime", r"at::native|__amd_rocclr"),
-    ("optimizer", r"adam_kernel|sgd_kernel|transpose_krsc|zero_f32|step_inc"),
+    ("optimizer", r"adam_kernel|sgd_kernel|adam_dev_kernel|sgd_dev_kernel|grad_sqnorm|sqnorm_sum|hyper_kernel|"
+                  r"transpose_krsc|zero_f32|step_inc"),
     ("conv wgrad", r"wgrad|splitk_finalize"),
     ("conv (stem)", r"conv_stem"),
     ("conv fwd/dgrad (halo)", r"conv3_halo_kernel|conv3_strip_kernel"),
