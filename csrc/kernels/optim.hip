@@ -233,14 +233,6 @@ __global__ __launch_bounds__(256) void hyper_kernel(const float* __restrict__ st
   hyper[HYPER_SUMSQ] = sumsq;
 }
 
-__global__ void cast_kernel(const float* __restrict__ x, bf16_t* __restrict__ y, int64_t n4) {
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n4;
-       i += (int64_t)gridDim.x * blockDim.x) {
-    const float4 f = ((const float4*)x)[i];
-    ((uint2*)y)[i] = make_uint2(pack2(f.x, f.y), pack2(f.z, f.w));
-  }
-}
-
 static int blocks_for(int64_t n4) {
   return (int)std::max<int64_t>(1, std::min<int64_t>((n4 + 255) / 256, 4096));
 }
@@ -296,11 +288,6 @@ void grad_sqnorm_sum(const float* part, int nparts, float* out, hipStream_t s) {
 void hyper_update(const float* step, const float* part, int nparts, float* hyper,
                   const HyperCfg& cfg, hipStream_t s) {
   hipLaunchKernelGGL(hyper_kernel, dim3(1), dim3(256), 0, s, step, part, nparts, hyper, cfg);
-}
-
-void cast_f32_bf16(const float* x, bf16_raw* y, int64_t n, hipStream_t s) {
-  const int64_t n4 = n / 4;
-  hipLaunchKernelGGL(cast_kernel, dim3(blocks_for(n4)), dim3(256), 0, s, x, y, n4);
 }
 
 static void step_inc_launch(float* step, hipStream_t s);

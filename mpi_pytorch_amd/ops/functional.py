@@ -160,6 +160,18 @@ def _run_wgrad(fn, *tensors) -> None:
     _SIDE["used"] = True
 
 
+def _conv_wgrad(k, g, x, w, conv) -> None:
+    """``conv``'s weight gradient of the output gradient ``g`` into ``w.grad`` (and its arena
+    notifications), through ``_run_wgrad``."""
+    sh, sw, ph, pw = conv.kgeom
+
+    def wgrad():  # (_fresh consumed on the side stream's turn, not at the call)
+        k.conv_wgrad(g, x, w.grad, sh, sw, ph, pw, overwrite=_fresh(w))
+        conv.fix_grad(w.grad)
+        _done(w)
+    _run_wgrad(wgrad, g, x)
+
+
 # ================================================================== branch stream (Inception)
 # Inside TrainStep's step (single GPU, eager), an Inception block's longest branch chain is
 # enqueued on a second stream and the block's other branches on the compute stream, joined
@@ -535,11 +547,7 @@ class _ConvBNAct(torch.autograd.Function):
             _done(gamma, beta)
         sh, sw, ph, pw = conv.kgeom
         if w.requires_grad:
-            def wgrad():
-                k.conv_wgrad(dz, x, w.grad, sh, sw, ph, pw, overwrite=_fresh(w))
-                conv.fix_grad(w.grad)
-                _done(w)
-            _run_wgrad(wgrad, dz, x)
+            _conv_wgrad(k, dz, x, w, conv)
         _done(ctx.bias)
         if dres_pair is not None:
             dres = dres_pair  # d/dz of the deferred BN's producer (see BNDefer.done)
@@ -744,27 +752,17 @@ class _ConvBNReLUPool(torch.autograd.Function):
         C = w.shape[0]
         stats = torch.empty(2, C, device=x.device, dtype=torch.float32)
         shift = _empty(x) if _NO_SHIFT else bn.running_mean
-        r = None
-        if (_STEM_POOL_FWD and x.is_cuda and b is None and tuple(cfg) == (3, 3, 2, 2, 1, 1, False)
-                and gamma is not None and beta is not None):
-            # the pool taken inside the stem conv kernel, BN + ReLU on the pooled extremes
-            r = k.conv_stem_pool_fwd(x, weight_of(w), sh, sw, ph, pw, stats, shift, gamma, beta,
-                                     bn.running_mean, bn.running_var, bn.momentum_value(),
-                                     bn.eps, bn.num_batches_tracked)
-        if r is not None:
-            y, idx, mean, rstd, z, zsel = r
-        else:
-            z = k.conv_fwd(x, weight_of(w), _or_empty(b, x), sh, sw, ph, pw, False, stats, shift)
-            # zsel: raw z at each window's argmax, so the backward's reduction pass reads only
-            # pooled-size tensors (maxpool_bn_bwd_sel_reduce_kernel)
-            N, H, W, C_ = z.shape
-            zsel = torch.empty(N, _pool_out(H, cfg[0], cfg[2], cfg[4], cfg[6]),
-                               _pool_out(W, cfg[1], cfg[3], cfg[5], cfg[6]), C_,
-                               device=z.device, dtype=z.dtype)
-            y, idx, mean, rstd = k.bn_relu_maxpool_fwd(z, stats, gamma, beta, bn.running_mean,
-                                                       bn.running_var, bn.momentum_value(),
-                                                       bn.eps, *cfg, bn.num_batches_tracked,
-                                                       zsel_out=zsel)
+        z = k.conv_fwd(x, weight_of(w), _or_empty(b, x), sh, sw, ph, pw, False, stats, shift)
+        # zsel: raw z at each window's argmax, so the backward's reduction pass reads only
+        # pooled-size tensors (maxpool_bn_bwd_sel_reduce_kernel)
+        N, H, W, C_ = z.shape
+        zsel = torch.empty(N, _pool_out(H, cfg[0], cfg[2], cfg[4], cfg[6]),
+                           _pool_out(W, cfg[1], cfg[3], cfg[5], cfg[6]), C_,
+                           device=z.device, dtype=z.dtype)
+        y, idx, mean, rstd = k.bn_relu_maxpool_fwd(z, stats, gamma, beta, bn.running_mean,
+                                                   bn.running_var, bn.momentum_value(),
+                                                   bn.eps, *cfg, bn.num_batches_tracked,
+                                                   zsel_out=zsel)
         ctx.conv = conv
         ctx.cfg = cfg
         ctx.bias = b
@@ -801,11 +799,7 @@ class _ConvBNReLUPool(torch.autograd.Function):
                               _sink(beta, dy), *ctx.cfg[:6], zsel=zsel)
         _done(gamma, beta)
         if w.requires_grad:
-            def wgrad():
-                k.conv_wgrad(dz, x, w.grad, sh, sw, ph, pw, overwrite=_fresh(w))
-                conv.fix_grad(w.grad)
-                _done(w)
-            _run_wgrad(wgrad, dz, x)
+            _conv_wgrad(k, dz, x, w, conv)
         _done(ctx.bias)
         dx = None
         if ctx.needs_input_grad[0]:
@@ -814,12 +808,9 @@ class _ConvBNReLUPool(torch.autograd.Function):
         return dx, None, None, None, None, None, None, None
 
 
-# (A/B switches) the stem's pool backward inside its weight gradient (on: 1.06 ms vs 1.63 ms
-# two-pass at batch 1024), and its pool forward inside the stem conv kernel (conv_stem.hip;
-# off: the 114 KB z image in LDS leaves one 4-wave block per CU, 1.64 ms vs 1.17 ms for
-# conv + bn_relu_maxpool_fwd - profiles/stem_pool_r6.txt)
+# (A/B switch) the stem's pool backward inside its weight gradient (on: 1.06 ms vs 1.63 ms
+# two-pass at batch 1024 - profiles/stem_pool_r6.txt)
 _STEM_POOL_WGRAD = os.environ.get("MPA_STEM_POOL_WGRAD", "1") == "1"
-_STEM_POOL_FWD = os.environ.get("MPA_STEM_POOL_FWD", "0") == "1"
 
 
 def conv_bn_relu_maxpool(x, conv, bn, pool):
@@ -905,11 +896,7 @@ class _ConvAct(torch.autograd.Function):
         _done(b)
         sh, sw, ph, pw = conv.kgeom
         if w.requires_grad:
-            def wgrad():
-                k.conv_wgrad(g, x, w.grad, sh, sw, ph, pw, overwrite=_fresh(w))
-                conv.fix_grad(w.grad)
-                _done(w)
-            _run_wgrad(wgrad, g, x)
+            _conv_wgrad(k, g, x, w, conv)
         dx = None
         if ctx.needs_input_grad[0]:
             li = ctx.link_in
