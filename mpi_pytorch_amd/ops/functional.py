@@ -74,6 +74,12 @@ def _done(*ps) -> None:
             grad_done(p)
 
 
+def _grads(fn, *grads):
+    """A backward's return value: ``grads`` for the leading inputs of ``fn.forward``, None for
+    every other argument."""
+    return grads + (None,) * (fn.forward.__code__.co_argcount - 1 - len(grads))
+
+
 # ================================================================ weight-gradient stream
 # Inside TrainStep's eager backward (single GPU; MPA_WGRAD_STREAM=0 turns it off), the conv
 # weight gradients run on a second HIP stream (+4 % ResNet-18, +2.7 % VGG-16 measured,
@@ -274,13 +280,32 @@ class GradJoin:
     extra read/read/write sweep of the activation per extra consumer.  Instead all
     consumers hold the same join, created with ``expected`` = their number.  Each backward
     that runs hands its contribution to the join and returns None for x, except the LAST
-    one, which returns the sum: a computed tensor (a pool or BN gradient) becomes the
-    running partial, a dgrad is parked as the deferred launch itself and later either
-    writes fresh or accumulates into the partial in its GEMM epilogue
-    (``conv_dgrad(..., accum=)``: fp32 add, one rounding per contribution).  A fresh write is
-    given to a dgrad that covers every pixel, so a 1x1/s2 downsample (three of four stride
-    phases without taps) never needs a zero fill.  Independent of autograd's execution
-    order (autograd runs x's producer only after every consumer's backward)."""
+    one, which returns the sum (``add``).  Independent of autograd's execution order
+    (autograd runs x's producer only after every consumer's backward).
+
+    A contribution is a computed tensor (a pool or BN gradient), a ``_MaskedRes`` (a
+    shortcut gradient dy * mask not yet written) or a ``_Dgrad`` (a conv dgrad not yet
+    launched, which can write fresh or accumulate in its GEMM epilogue:
+    ``conv_dgrad(..., accum=)``, fp32 add, one rounding per contribution).  How the
+    running partial and a newcomer combine (``_combine``):
+
+    ==============  ===================  ======================  ==========================
+    partial         + tensor             + _MaskedRes            + _Dgrad
+    ==============  ===================  ======================  ==========================
+    (none)          kept                 kept unwritten (*)      parked (*)
+    tensor          ``add_bf16_``        written, ``add_bf16_``  launched, accum = partial
+    _MaskedRes      written,             both written,           ``conv_dgrad_res`` (stride
+                    ``add_bf16_``        ``add_bf16_``           1, transposed weight), else
+                                                                 written, then as a tensor
+    parked _Dgrad   launched,            written, then as a      ``conv_dgrad_pair`` (_PAIR,
+                    accum = tensor       tensor                  one of the two full), else
+                                                                 two launches (**)
+    ==============  ===================  ======================  ==========================
+
+    (*)  the last contribution never stays pending: it is written / launched fresh.
+    (**) the fresh write goes to a dgrad that covers every pixel and the other accumulates
+         into it, so a 1x1/s2 downsample (three of four stride phases without taps) never
+         needs a zero fill; when both or neither are full, the newcomer writes fresh."""
 
     __slots__ = ("partial", "expected", "arrived")
 
@@ -289,26 +314,34 @@ class GradJoin:
         self.expected = int(expected)
         self.arrived = 0
 
-    def take(self):
-        p, self.partial = self.partial, None
-        return p
-
-    def arrive(self) -> bool:
-        """Count one contribution; True when it is the last."""
+    def add(self, k, c):
+        """Hand in one contribution; the sum if it is the last one, else None."""
         self.arrived += 1
-        return self.arrived >= self.expected
+        last = self.arrived >= self.expected
+        prev, self.partial = self.partial, None
+        acc = _combine(k, prev, c, last)
+        if last:
+            return acc
+        self.partial = acc
+        return None
 
 
-class _Deferred:
-    """A parked dgrad: ``run(accum)`` launches it (fresh when accum is None); ``args`` =
-    (dz, w, wt, conv) lets the next contribution merge it into its own launch."""
+class _Dgrad:
+    """A conv dgrad not yet launched: ``run(accum)`` launches it (fresh when accum is None);
+    ``full``: every pixel of dx receives taps (no tap-less stride phase)."""
 
-    __slots__ = ("run", "full", "args")
+    __slots__ = ("k", "dz", "w", "wt", "conv", "in_hw", "full")
 
-    def __init__(self, run, full: bool, args=None):
-        self.run = run
-        self.full = full
-        self.args = args
+    def __init__(self, k, dz, w, wt, conv, in_hw):
+        self.k, self.dz, self.w, self.wt, self.conv, self.in_hw = k, dz, w, wt, conv, in_hw
+        sh, sw = conv.kgeom[:2]
+        R, S = conv.weight.shape[1:3]
+        self.full = sh <= R and sw <= S
+
+    def run(self, accum=None):
+        sh, sw, ph, pw = self.conv.kgeom
+        return self.k.conv_dgrad(self.dz, self.w, self.in_hw[0], self.in_hw[1], sh, sw, ph, pw,
+                                 self.wt, accum)
 
 
 # MPA_DGRAD_PAIR=0: a residual stage's conv1 (3x3/s2) and 1x1/s2 shortcut dgrads run as two
@@ -316,21 +349,17 @@ class _Deferred:
 _PAIR = os.environ.get("MPA_DGRAD_PAIR", "1") == "1"
 
 
-def _dgrad_pair(k, a, b, in_hw):
-    """Both parked/current dgrads of one activation in one launch (``conv_dgrad_pair``):
-    a = (dz, w, wt, conv) of a conv whose taps cover every pixel, b = the other."""
-    dz, w, wt, conv = a
-    dz2, w2, wt2, conv2 = b
-    sh, sw, ph, pw = conv.kgeom
-    sh2, sw2, ph2, pw2 = conv2.kgeom
-    if (sh, sw) != (sh2, sw2) or (dz.is_cuda and (wt is None or wt2 is None)):
+def _dgrad_pair(k, a: _Dgrad, b: _Dgrad):
+    """Both dgrads of one activation in one launch (``conv_dgrad_pair``): ``a`` covers every
+    pixel, ``b`` is the other.  None when the merged launch does not apply."""
+    sh, sw, ph, pw = a.conv.kgeom
+    sh2, sw2, ph2, pw2 = b.conv.kgeom
+    if (sh, sw) != (sh2, sw2) or (a.dz.is_cuda and (a.wt is None or b.wt is None)):
         return None
-    if tuple(dz.shape) != tuple(dz2.shape) or w.shape[3] != w2.shape[3]:
+    if tuple(a.dz.shape) != tuple(b.dz.shape) or a.w.shape[3] != b.w.shape[3]:
         return None
-    if not hasattr(k, "conv_dgrad_pair"):
-        return None
-    return k.conv_dgrad_pair(dz, w, wt, in_hw[0], in_hw[1], sh, sw, ph, pw, dz2, w2, wt2,
-                             ph2, pw2)
+    return k.conv_dgrad_pair(a.dz, a.w, a.wt, a.in_hw[0], a.in_hw[1], sh, sw, ph, pw,
+                             b.dz, b.w, b.wt, ph2, pw2)
 
 
 class _MaskedRes:
@@ -344,7 +373,7 @@ class _MaskedRes:
         self.dy = dy
         self.mask = mask
 
-    def materialize(self, k):
+    def materialize(self):
         if not self.dy.is_cuda:
             return (self.dy.float() * ref.bitmask_unpack(self.mask, self.dy.shape)).to(
                 self.dy.dtype)
@@ -358,84 +387,71 @@ class _MaskedRes:
 _RES_MASK = os.environ.get("MPA_RES_MASK", "1") == "1"
 
 
-def _join_grad(join: Optional[GradJoin], t):
-    """Offer a computed contribution ``t`` (a tensor or a _MaskedRes) to ``join``; returns
-    what the op hands back to autograd (the sum if it is the last contribution, else None)."""
-    if join is None or t is None:
-        return t
-    last = join.arrive()
-    prev = join.take()
-    if isinstance(t, _MaskedRes) and (last or prev is not None):
-        t = t.materialize(None)
-    if isinstance(prev, _MaskedRes):
-        prev = prev.materialize(None)
-    if prev is None:
-        acc = t
-    elif isinstance(prev, _Deferred):
-        acc = prev.run(t)  # the parked dgrad accumulates into t
-    else:  # two computed tensors (Inception's Mixed_7a maxpool + aux-head avg-pool)
-        acc = prev.contiguous()
-        K(acc).add_bf16_(acc, t.contiguous())
-    if last:
-        return acc
-    join.partial = acc
-    return None
-
-
-def _dgrad_full(conv, in_hw) -> bool:
-    """Every pixel of dx receives taps (no tap-less stride phase)."""
-    sh, sw = conv.kgeom[:2]
-    R, S = conv.weight.shape[1:3]
-    return sh <= R and sw <= S
-
-
-def _dgrad_joined(k, join: Optional[GradJoin], dz, w, in_hw, conv, wt):
-    """conv dgrad, summed with the join's other contributions (see GradJoin)."""
-    sh, sw, ph, pw = conv.kgeom
-
-    def run(acc):
-        return k.conv_dgrad(dz, w, in_hw[0], in_hw[1], sh, sw, ph, pw, wt, acc)
-
-    if join is None:
-        return run(None)
-    last = join.arrive()
-    prev = join.take()
-    full = _dgrad_full(conv, in_hw)
-    args = (dz, w, wt, conv)
-    if isinstance(prev, _MaskedRes):
-        acc = None
-        sh, sw, ph, pw = conv.kgeom
-        if sh == 1 and sw == 1 and hasattr(k, "conv_dgrad_res") and (wt is not None
-                                                                    or not dz.is_cuda):
-            acc = k.conv_dgrad_res(dz, w, wt, in_hw[0], in_hw[1], ph, pw, prev.dy, prev.mask)
-        if acc is None:
-            acc = run(prev.materialize(k))
-        if last:
-            return acc
-        join.partial = acc
+def _dgrad_res(k, d: _Dgrad, res: _MaskedRes):
+    """``d`` with the unwritten shortcut gradient ``res`` added in its epilogue
+    (``conv_dgrad_res``).  None when the fused launch does not apply."""
+    sh, sw, ph, pw = d.conv.kgeom
+    if (sh, sw) != (1, 1) or (d.wt is None and d.dz.is_cuda):
         return None
+    return k.conv_dgrad_res(d.dz, d.w, d.wt, d.in_hw[0], d.in_hw[1], ph, pw, res.dy, res.mask)
+
+
+def _combine(k, prev, new, last: bool):
+    """``prev`` (a join's partial, or None) + ``new`` by GradJoin's table; ``last``: nothing
+    follows ``new``.  Returns the sum as a tensor, or a first arrival left pending."""
+    if isinstance(new, _MaskedRes) and (last or prev is not None):
+        new = new.materialize()
     if prev is None:
-        if last:
-            return run(None)
-        join.partial = _Deferred(run, full, args)
-        return None
-    if isinstance(prev, _Deferred):
-        acc = None
-        if _PAIR and prev.args is not None and full != prev.full:
-            acc = (_dgrad_pair(k, args, prev.args, in_hw) if full
-                   else _dgrad_pair(k, prev.args, args, in_hw))
+        return new.run() if (last and isinstance(new, _Dgrad)) else new
+    parked, dgrad = isinstance(prev, _Dgrad), isinstance(new, _Dgrad)
+    if isinstance(prev, _MaskedRes):
+        acc = _dgrad_res(k, new, prev) if dgrad else None
         if acc is not None:
-            pass
-        elif full or not prev.full:
-            acc = prev.run(run(None))
-        else:
-            acc = run(prev.run(None))
-    else:
-        acc = run(prev)
-    if last:
-        return acc
-    join.partial = acc
-    return None
+            return acc
+        prev = prev.materialize()
+    if parked and dgrad:
+        acc = None
+        if _PAIR and new.full != prev.full:
+            acc = _dgrad_pair(k, new, prev) if new.full else _dgrad_pair(k, prev, new)
+        if acc is not None:
+            return acc
+        if new.full or not prev.full:
+            return prev.run(new.run())
+        return new.run(prev.run())
+    if parked:
+        return prev.run(new)  # (accumulates into the newcomer)
+    if dgrad:
+        return new.run(prev)
+    acc = prev.contiguous()  # (Inception's Mixed_7a maxpool + aux-head avg-pool)
+    k.add_bf16_(acc, new.contiguous())
+    return acc
+
+
+def _input_grad(k, g, w, conv, in_hw, join: Optional[GradJoin] = None,
+                link: Optional[BNLink] = None, reduce_joined: bool = True):
+    """What a conv op returns for its input x, from its output gradient ``g``.  ``link``
+    (the BNLink of x's producer, a ReLU(BN)) selects a dgrad that also runs the producer's
+    BN-backward reduction, leaving the sums in ``link.sums``: into a DenseNet block gradient
+    (``link.gacc``: nothing is returned), or as dx * mask, which then goes through ``join``
+    as a tensor - unless ``reduce_joined`` is off, when a join rules the fused reduction
+    out.  Otherwise the plain dgrad, through ``join`` if there is one."""
+    li = link
+    wb, wt = weight_of(w), weight_t_of(w)
+    gacc = li is not None and li.gacc is not None
+    bnred = li is not None and li.z is not None and (join is None or reduce_joined)
+    if ((gacc or bnred) and (wt is not None or not g.is_cuda)
+            and k.conv_bnred_ok(w.shape[0], w.shape[3])):
+        if gacc:
+            li.sums = k.conv_dgrad_bnred_gacc(g, wb, wt, li.z, li.mean, li.rstd, li.gamma,
+                                              li.beta, li.gacc)
+            return None
+        sh, sw, ph, pw = conv.kgeom
+        dx, li.sums = k.conv_dgrad_bnred(g, wb, in_hw[0], in_hw[1], sh, sw, ph, pw, wt, li.z,
+                                         _or_empty(li.y, g), li.mean, li.rstd, gamma=li.gamma,
+                                         beta=li.beta)
+        return dx if join is None else join.add(k, dx)
+    d = _Dgrad(k, g, wb, wt, conv, in_hw)
+    return d.run() if join is None else join.add(k, d)
 
 
 class _ConvBNAct(torch.autograd.Function):
@@ -495,10 +511,51 @@ class _ConvBNAct(torch.autograd.Function):
         return y
 
     @staticmethod
+    def _bn_backward(ctx, k, dy, z, y, mean, rstd, ymask, lo, want_g):
+        """The BN (+ residual, ReLU) backward in the one form that applies.  Returns
+        (dz, g, dres_pair): ``g`` = the residual's gradient dy * mask if ``want_g`` (a tensor,
+        or a _MaskedRes left unwritten), ``dres_pair`` = d/dz of the deferred BN that produced
+        the residual, when ``bn_bwd_pair`` ran that BN's backward too."""
+        gamma, beta = ctx.params[1:]
+        rd = ctx.res_defer
+        if ctx.defer is not None and ctx.defer.done:
+            # the consumer's bn_bwd_pair already ran this BN's backward: dy IS d/dz, and the
+            # affine gradients are in place
+            ctx.defer.done = False
+            return dy, None, None
+        if (rd is not None and rd.z is not None and ctx.needs_input_grad[1]
+                and ctx.join_res is None):
+            g2, b2 = rd.gamma, rd.beta
+            dz, dres_pair = k.bn_bwd_pair(dy, z, ymask, mean, rstd, gamma, _sink(gamma, dy),
+                                          _sink(beta, dy), rd.z, rd.mean, rd.rstd, g2,
+                                          _sink(g2, dy), _sink(b2, dy))
+            _done(g2, b2)
+            rd.done = True
+            rd.z = None
+            return dz, None, dres_pair
+        if lo is not None and lo.sums is not None:
+            # the consumer's dgrad already masked dy and reduced (sum g, sum g*xhat)
+            dz, g = k.bn_bwd_apply(dy, z, _empty(dy), mean, rstd, gamma, _sink(gamma, dy),
+                                   _sink(beta, dy), lo.sums, True, want_g)
+            lo.sums = None
+            return dz, g, None
+        if ctx.relu and not ctx.has_res and beta is not None:
+            # relu(bn(z)) without a residual: the mask is recomputed from z, y is not read
+            dz, g = k.bn_bwd(dy, z, _empty(dy), mean, rstd, gamma, _sink(gamma, dy),
+                             _sink(beta, dy), True, want_g, beta)
+            return dz, g, None
+        # identity shortcut: conv1's dgrad adds dy * mask in its epilogue (_MaskedRes), so
+        # g is not written here
+        mres = (want_g and _RES_MASK and ymask is not None and ctx.join_res is not None
+                and ctx.join_res.arrived == 0 and ctx.join_res.partial is None)
+        dz, g = k.bn_bwd(dy, z, _or_empty(y, dy), mean, rstd, gamma, _sink(gamma, dy),
+                         _sink(beta, dy), True, want_g and not mres, ymask=ymask)
+        return dz, (_MaskedRes(dy, ymask) if mres else g), None
+
+    @staticmethod
     def backward(ctx, dy):
         x, z, y, mean, rstd, ymask = ctx.saved_tensors
         w, gamma, beta = ctx.params
-        conv = ctx.conv
         k = K(dy)
         dy = _rows(dy)
         want_g = bool(ctx.has_res and ctx.needs_input_grad[1])
@@ -509,71 +566,18 @@ class _ConvBNAct(torch.autograd.Function):
         # inside steps_without_gc.  The consumer's backward has run by now, so the node lets
         # go of the link and reference counting frees the step's activations again.
         ctx.link_out = None
-        rd = ctx.res_defer
-        dres_pair = None
-        if ctx.defer is not None and ctx.defer.done:
-            # the consumer's bn_bwd_pair already ran this BN's backward: dy IS d/dz, and the
-            # affine gradients are in place
-            dz = dy
-            ctx.defer.done = False
-        elif (rd is not None and rd.z is not None and ctx.needs_input_grad[1]
-                and ctx.join_res is None and hasattr(k, "bn_bwd_pair")):
-            g2, b2 = rd.gamma, rd.beta
-            dz, dres_pair = k.bn_bwd_pair(dy, z, ymask, mean, rstd, gamma, _sink(gamma, dy),
-                                          _sink(beta, dy), rd.z, rd.mean, rd.rstd, g2,
-                                          _sink(g2, dy), _sink(b2, dy))
-            _done(g2, b2)
-            rd.done = True
-            rd.z = None
-        elif lo is not None and lo.sums is not None:
-            # the consumer's dgrad already masked dy and reduced (sum g, sum g*xhat)
-            dz, g = k.bn_bwd_apply(dy, z, _empty(dy), mean, rstd, gamma, _sink(gamma, dy),
-                                   _sink(beta, dy), lo.sums, True, want_g)
-            lo.sums = None
-        elif ctx.relu and not ctx.has_res and beta is not None:
-            # relu(bn(z)) without a residual: the mask is recomputed from z, y is not read
-            dz, g = k.bn_bwd(dy, z, _empty(dy), mean, rstd, gamma, _sink(gamma, dy),
-                             _sink(beta, dy), True, want_g, beta)
-        else:
-            # identity shortcut: conv1's dgrad adds dy * mask in its epilogue (_MaskedRes), so
-            # g is not written here
-            mres = (want_g and _RES_MASK and ymask is not None and ctx.join_res is not None
-                    and ctx.join_res.arrived == 0 and ctx.join_res.partial is None)
-            dz, g = k.bn_bwd(dy, z, _or_empty(y, dy), mean, rstd, gamma, _sink(gamma, dy),
-                             _sink(beta, dy), True, want_g and not mres, ymask=ymask)
-            if mres:
-                g = _MaskedRes(dy, ymask)
+        dz, g, dres = _ConvBNAct._bn_backward(ctx, k, dy, z, y, mean, rstd, ymask, lo, want_g)
         if ctx.defer is None or dz is not dy:
             _done(gamma, beta)
-        sh, sw, ph, pw = conv.kgeom
         if w.requires_grad:
-            _conv_wgrad(k, dz, x, w, conv)
+            _conv_wgrad(k, dz, x, w, ctx.conv)
         _done(ctx.bias)
-        if dres_pair is not None:
-            dres = dres_pair  # d/dz of the deferred BN's producer (see BNDefer.done)
-        else:
-            dres = g if (ctx.has_res and ctx.needs_input_grad[1]) else None
-            dres = _join_grad(ctx.join_res, dres)
+        if dres is None and want_g:  # (else d/dz of the deferred BN's producer: BNDefer.done)
+            dres = g if ctx.join_res is None else ctx.join_res.add(k, g)
         dx = None
         if ctx.needs_input_grad[0]:
-            li = ctx.link_in
-            wt = weight_t_of(w)
-            if (li is not None and li.gacc is not None and (wt is not None or not dz.is_cuda)
-                    and k.conv_bnred_ok(w.shape[0], w.shape[3])):
-                li.sums = k.conv_dgrad_bnred_gacc(dz, weight_of(w), wt, li.z, li.mean, li.rstd,
-                                                  li.gamma, li.beta, li.gacc)
-                dx = None
-            elif (li is not None and li.z is not None and (wt is not None or not dz.is_cuda)
-                    and k.conv_bnred_ok(w.shape[0], w.shape[3])):
-                dx, li.sums = k.conv_dgrad_bnred(dz, weight_of(w), ctx.in_hw[0], ctx.in_hw[1],
-                                                 sh, sw, ph, pw, wt, li.z,
-                                                 _or_empty(li.y, dz), li.mean, li.rstd,
-                                                 gamma=li.gamma, beta=li.beta)
-                dx = _join_grad(ctx.join_x, dx)
-            else:
-                dx = _dgrad_joined(k, ctx.join_x, dz, weight_of(w), ctx.in_hw, conv, wt)
-        return (dx, dres, None, None, None, None, None, None, None, None, None, None, None, None,
-                None, None)
+            dx = _input_grad(k, dz, w, ctx.conv, ctx.in_hw, ctx.join_x, ctx.link_in)
+        return _grads(_ConvBNAct, dx, dres)
 
 
 def _rows(t: torch.Tensor) -> torch.Tensor:
@@ -695,7 +699,9 @@ class _ConvGroupBNAct(torch.autograd.Function):
             _run_wgrad(wgrad, dz, x)
         dx = None
         if ctx.needs_input_grad[0]:
-            dx = _dgrad_joined(k, ctx.join, dz, ctx.W, ctx.in_hw, ctx.mods[0].conv, None)
+            # (the joint weight is an arena view with no transposed copy: the plain dgrad)
+            d = _Dgrad(k, dz, ctx.W, None, ctx.mods[0].conv, ctx.in_hw)
+            dx = d.run() if ctx.join is None else ctx.join.add(k, d)
         ctx.W = None
         return (dx, None, None, None, None) + (None,) * ctx.nparams
 
@@ -794,7 +800,7 @@ class _ConvBNReLUPool(torch.autograd.Function):
                 conv.fix_grad(w.grad)
                 _done(w)
             _run_wgrad(wgrad, dy, idx, z, x, mean, rstd, sums)
-            return None, None, None, None, None, None, None, None
+            return _grads(_ConvBNReLUPool)
         dz = k.maxpool_bn_bwd(dy, idx, z, mean, rstd, gamma, beta, _sink(gamma, dy),
                               _sink(beta, dy), *ctx.cfg[:6], zsel=zsel)
         _done(gamma, beta)
@@ -803,9 +809,8 @@ class _ConvBNReLUPool(torch.autograd.Function):
         _done(ctx.bias)
         dx = None
         if ctx.needs_input_grad[0]:
-            dx = k.conv_dgrad(dz, weight_of(w), ctx.in_hw[0], ctx.in_hw[1], sh, sw, ph, pw,
-                              weight_t_of(w))
-        return dx, None, None, None, None, None, None, None
+            dx = _input_grad(k, dz, w, conv, ctx.in_hw)
+        return _grads(_ConvBNReLUPool, dx)
 
 
 # (A/B switch) the stem's pool backward inside its weight gradient (on: 1.06 ms vs 1.63 ms
@@ -894,22 +899,13 @@ class _ConvAct(torch.autograd.Function):
         else:
             g = k.act_bwd(dy, _or_empty(y, dy), _sink(b, dy))
         _done(b)
-        sh, sw, ph, pw = conv.kgeom
         if w.requires_grad:
             _conv_wgrad(k, g, x, w, conv)
         dx = None
         if ctx.needs_input_grad[0]:
-            li = ctx.link_in
-            wt = weight_t_of(w)
-            if (li is not None and li.z is not None and ctx.join is None
-                    and (wt is not None or not g.is_cuda)
-                    and k.conv_bnred_ok(w.shape[0], w.shape[3])):
-                dx, li.sums = k.conv_dgrad_bnred(g, weight_of(w), ctx.in_hw[0], ctx.in_hw[1],
-                                                 sh, sw, ph, pw, wt, li.z, _or_empty(li.y, g),
-                                                 li.mean, li.rstd, gamma=li.gamma, beta=li.beta)
-            else:
-                dx = _dgrad_joined(k, ctx.join, g, weight_of(w), ctx.in_hw, conv, wt)
-        return dx, None, None, None, None, None, None, None, None, None, None
+            dx = _input_grad(k, g, w, conv, ctx.in_hw, ctx.join, ctx.link_in,
+                             reduce_joined=False)
+        return _grads(_ConvAct, dx)
 
 
 def conv_act(x, conv, relu: bool = False, join: Optional[GradJoin] = None,
@@ -1031,9 +1027,8 @@ class _LinearAct(torch.autograd.Function):
         k = K(dy)
         dy = _padded_grad(dy, w.shape[0])
         g = k.act_bwd(dy, _or_empty(y, dy), _sink(b, dy))
-        # dgrad before the weight gradient's notify: once every gradient of a classifier is
-        # final, its optimizer update may start on a side stream (TrainStep's early head
-        # update) - nothing may read the old bf16 weight after that point
+        # dgrad before the weight gradient: the rest of the backward chain waits for dx,
+        # nothing waits for w.grad before its bucket closes
         dx = (k.linear_dgrad(g, weight_of(w), weight_t_of(w)) if ctx.needs_input_grad[0]
               else None)
         _done(b)
@@ -1085,15 +1080,15 @@ class _MaxPool(torch.autograd.Function):
         k = K(dy)
         dy = dy.contiguous()
         li = ctx.link_in
-        if li is not None and ctx.join is None and hasattr(k, "maxpool_bwd_relu"):
+        if li is not None and ctx.join is None:
             # the input is a ReLU output whose producer handed its backward over (BNLink):
             # route only where the pooled value is > 0 and return the producer's bias sums
             r = k.maxpool_bwd_relu(dy, idx, y, ctx.hw[0], ctx.hw[1], *ctx.cfg[:6])
             if r is not None:
                 li.sums = r[1]
-                return r[0], None, None, None
+                return _grads(_MaxPool, r[0])
         dx = k.maxpool_bwd(dy, idx, ctx.hw[0], ctx.hw[1], *ctx.cfg)
-        return _join_grad(ctx.join, dx), None, None, None
+        return _grads(_MaxPool, dx if ctx.join is None else ctx.join.add(k, dx))
 
 
 def max_pool2d(x, kernel, stride, padding=(0, 0), ceil_mode=False,
@@ -1117,8 +1112,9 @@ class _AvgPool(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dy):
-        dx = K(dy).avgpool_bwd(dy.contiguous(), ctx.hw[0], ctx.hw[1], *ctx.cfg)
-        return _join_grad(ctx.join, dx), None, None
+        k = K(dy)
+        dx = k.avgpool_bwd(dy.contiguous(), ctx.hw[0], ctx.hw[1], *ctx.cfg)
+        return _grads(_AvgPool, dx if ctx.join is None else ctx.join.add(k, dx))
 
 
 def avg_pool2d(x, kernel, stride, padding=(0, 0), ceil_mode=False, count_include_pad=True,

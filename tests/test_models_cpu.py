@@ -188,9 +188,9 @@ def test_grad_join_order_independent(order):
     exp = ref.conv_dgrad(dz, w3, 10, 10, 2, 2, 1, 1) + ref.conv_dgrad(dz, w1, 10, 10, 2, 2, 0, 0)
     j = Fn.GradJoin()
     calls = [(w3, c3), (w1, c1)] if order == "conv_first" else [(w1, c1), (w3, c3)]
-    r0 = Fn._dgrad_joined(ref, j, dz, calls[0][0], (10, 10), calls[0][1], None)
+    r0 = j.add(ref, Fn._Dgrad(ref, dz, calls[0][0], None, calls[0][1], (10, 10)))
     assert r0 is None and j.partial is not None
-    r1 = Fn._dgrad_joined(ref, j, dz, calls[1][0], (10, 10), calls[1][1], None)
+    r1 = j.add(ref, Fn._Dgrad(ref, dz, calls[1][0], None, calls[1][1], (10, 10)))
     assert j.partial is None
     assert torch.allclose(r1, exp, rtol=1e-4, atol=1e-4)
 
