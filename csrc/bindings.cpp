@@ -1462,7 +1462,7 @@ void step_inc(Tensor step) {
 // pad: (top, bottom, left, right) zero border of the output canvas (empty = none)
 Tensor preprocess(Tensor img, int64_t OH, int64_t OW, std::vector<double> mean,
                   std::vector<double> stdv, int64_t mode, int64_t cpad, std::vector<int64_t> pad,
-                  c10::optional<Tensor> ext) {
+                  c10::optional<Tensor> ext, c10::optional<Tensor> box) {
   CHECK_CUDA(img);
   CHECK_CONTIG(img);
   TORCH_CHECK(img.scalar_type() == torch::kUInt8 && img.dim() == 4 && img.size(3) == 3,
@@ -1489,8 +1489,22 @@ Tensor preprocess(Tensor img, int64_t OH, int64_t OW, std::vector<double> mean,
                 "preprocess: ext must be int32 [B,2]");
     extp = ext->data_ptr<int>();
   }
+  const int* boxp = nullptr;
+  if (box && box->defined()) {
+    // per-image crop boxes (y0, x0, h, w, flip); like the extents, the caller
+    // (ops/functional.py) checked them against the extents on its host copy - the kernel
+    // trusts them
+    TORCH_CHECK(mode == 0, "preprocess: crop boxes with mode 0 only");
+    CHECK_CUDA((*box));
+    CHECK_CONTIG((*box));
+    TORCH_CHECK(box->scalar_type() == torch::kInt32 && box->dim() == 2 && box->size(0) == B &&
+                    box->size(1) == 5,
+                "preprocess: box must be int32 [B,5]");
+    TORCH_CHECK(box->device() == img.device(), "preprocess: box on another device");
+    boxp = box->data_ptr<int>();
+  }
   mpa::preprocess(img.data_ptr<uint8_t>(), B, H, W, OH, OW, n, mode, cpad, pd, bpm(out),
-                  cur_stream(), extp);
+                  cur_stream(), extp, boxp);
   return out;
 }
 
@@ -1851,7 +1865,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("preprocess_pil", &preprocess_pil, "PIL-exact bicubic resize + ToTensor + Normalize");
   m.def("preprocess", &preprocess, py::arg("img"), py::arg("OH"), py::arg("OW"), py::arg("mean"),
         py::arg("std"), py::arg("mode"), py::arg("cpad"),
-        py::arg("pad") = std::vector<int64_t>{}, py::arg("ext") = py::none());
+        py::arg("pad") = std::vector<int64_t>{}, py::arg("ext") = py::none(),
+        py::arg("box") = py::none());
   m.def("dropout_fwd", &dropout_fwd, py::arg("x"), py::arg("p"), py::arg("seed"),
         py::arg("offset"), py::arg("counter") = py::none());
   m.def("dropout_bwd", &dropout_bwd);

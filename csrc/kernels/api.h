@@ -449,8 +449,12 @@ struct OutPad {
 };
 void preprocess_set_copy(int on);  // identity-size fast path on/off (tests, A/B)
 // ext (optional): per-image source extents [B][2] = (h, w) inside the [H][W] pitch (mode 0)
+// box (optional, mode 0 only): per-image crop boxes [B][5] = (y0, x0, h, w, flip) in source
+// pixels of image b's slot; image b is resized from its box (which must lie inside its
+// extent - the caller checks, the kernel does not) and mirrored along W when flip != 0
 void preprocess(const uint8_t* img, int B, int H, int W, int OH, int OW, Norm3 nrm, int mode,
-                int cpad, OutPad pad, bf16_raw* out, hipStream_t s, const int* ext = nullptr);
+                int cpad, OutPad pad, bf16_raw* out, hipStream_t s, const int* ext = nullptr,
+                const int* box = nullptr);
 // PIL-exact bicubic (eval transform): per-image extents ext [B][2] (h, w) inside the
 // [Hp][Wp] pitch (nullptr: all full), per-image table selectors sel [B][2]; tmp holds
 // B * Hp * OW RGBx words

@@ -59,9 +59,24 @@ __device__ __forceinline__ void store_px(bf16_t* o, float c0, float c1, float c2
 constexpr int PP_ROWS = 8;
 constexpr int PP_MAXW = 1344;  // 2 x 8 staged rows x 1344 px x 3 B = 63 KiB of LDS
 
+// BOX (random-resized-crop + flip, the training augmentation): image b is resized from its
+// crop box (y0, x0, h, w) instead of its extent, and mirrored when flip is set.  All the
+// interpolation arithmetic is box-relative - (h, w) stand where the extent's (ih, iw) do,
+// taps clamp to the box edge - so a boxed launch is bitwise the plain launch of the
+// contiguous crop; (y0, x0) enter only the addresses.  Staging copies just the crop's byte
+// span [x0*3, (x0+w)*3) of a tap row: the vector loads start at the span start rounded
+// down to VEC (rows are VEC-aligned and W*3 % VEC == 0, so the rounded span stays inside
+// the row) and the slack bytes become an LDS offset of phase 2's tap pointers.  The LDS
+// pitch stays the slot's.  flip: output column ox takes the unflipped column OW-1-ox (a
+// mirror of the resize's result, torchvision's RandomResizedCrop -> RandomHorizontalFlip).
+// The box is trusted: the host (ops/functional.py) checked it against the extent, which it
+// replaces - a BOX instantiation takes the [B][5] boxes in ext's place.  Everything the
+// box adds sits under "if constexpr (BOX)", so the plain instantiations compile to the
+// code they had before there were boxes.
+//
 // VEC: staging load width (16, 4 or 1 bytes; alignment of the source rows); CPAD: 4 or 8
 // output channels with one 8-B / 16-B store per pixel, 0 = any (scalar stores)
-template <bool STAGED, int VEC, int CPAD>
+template <bool STAGED, int VEC, int CPAD, bool BOX = false>
 __global__ __launch_bounds__(256) void preprocess_bilinear_kernel(
     const uint8_t* __restrict__ img, int B, int H, int W, int OH, int OW,
     Norm3 nrm, int cpad_rt, OutPad pd, bf16_t* __restrict__ out, const int* __restrict__ ext) {
@@ -84,10 +99,16 @@ __global__ __launch_bounds__(256) void preprocess_bilinear_kernel(
     const int nrows = min(PP_ROWS, ohp - row0);
     const uint8_t* base = img + (size_t)b * H * W * 3;
     // this image's extent inside the [H][W] pitch (real images of different sizes share
-    // one padded slot); the full pitch when ext is null
-    const int ih = ext ? ext[2 * b] : H, iw = ext ? ext[2 * b + 1] : W;
+    // one padded slot); the full pitch when ext is null; BOX: the crop's size
+    const int ih = BOX ? ext[5 * b + 2] : ext ? ext[2 * b] : H;
+    const int iw = BOX ? ext[5 * b + 3] : ext ? ext[2 * b + 1] : W;
     const float sh = (float)ih / OH, sw = (float)iw / OW;
-    const int per = (iw * 3 + vec - 1) / vec;  // vectors per staged source row
+    // BOX: crop origin, mirror, and the bytes between the VEC-aligned start of the staging
+    // loads and the crop's first byte (all 0 and unused otherwise)
+    const int by0 = BOX ? ext[5 * b] : 0, bx0 = BOX ? ext[5 * b + 1] : 0;
+    const int flip = BOX ? ext[5 * b + 4] : 0, slack = BOX ? (bx0 * 3) & (vec - 1) : 0;
+    // vectors per staged source row
+    const int per = BOX ? (slack + iw * 3 + vec - 1) / vec : (iw * 3 + vec - 1) / vec;
     auto tap_rows = [&](int r, int& y0, int& y1, float& ly) {
       const int oy = row0 + r - pd.top;
       const float sy = fmaxf((oy + 0.5f) * sh - 0.5f, 0.f);
@@ -114,6 +135,7 @@ __global__ __launch_bounds__(256) void preprocess_bilinear_kernel(
           float ly;
           tap_rows(rt >> 1, y0, y1, ly);
           const uint8_t* src = base + (size_t)((rt & 1) ? y1 : y0) * rb;
+          if constexpr (BOX) src += (size_t)by0 * rb + (bx0 * 3 - slack);
           dsto[k] = rt * rbp + e * vec;
           if constexpr (vec == 16) v[k] = ((const uint4*)src)[e];
           else if constexpr (vec == 4) v[k].x = ((const uint32_t*)src)[e];
@@ -141,9 +163,14 @@ __global__ __launch_bounds__(256) void preprocess_bilinear_kernel(
       if constexpr (STAGED) {
         t0 = srow + (2 * r) * rbp;
         t1 = srow + (2 * r + 1) * rbp;
+        if constexpr (BOX) t0 += slack, t1 += slack;
       } else {
         t0 = base + (size_t)y0 * rb;
         t1 = base + (size_t)y1 * rb;
+        if constexpr (BOX) {
+          t0 += (size_t)by0 * rb + bx0 * 3;
+          t1 += (size_t)by0 * rb + bx0 * 3;
+        }
       }
       for (int px = threadIdx.x; px < owp; px += blockDim.x) {
         const int ox = px - pd.left;
@@ -152,7 +179,13 @@ __global__ __launch_bounds__(256) void preprocess_bilinear_kernel(
           store_px(o, 0.f, 0.f, 0.f, cpad);
           continue;
         }
-        const float sx = fmaxf((ox + 0.5f) * sw - 0.5f, 0.f);
+        float sx;
+        if constexpr (BOX) {  // rx: this pixel's column in the unflipped resize
+          const int rx = flip ? OW - 1 - ox : ox;
+          sx = fmaxf((rx + 0.5f) * sw - 0.5f, 0.f);
+        } else {
+          sx = fmaxf((ox + 0.5f) * sw - 0.5f, 0.f);
+        }
         const int x0 = min((int)sx, iw - 1), x1 = min(x0 + 1, iw - 1);
         const float lx = sx - x0;
         float c[3];
@@ -431,10 +464,11 @@ static int g_pre_copy = [] {
 void preprocess_set_copy(int on) { g_pre_copy = on; }
 
 void preprocess(const uint8_t* img, int B, int H, int W, int OH, int OW, Norm3 nrm, int mode,
-                int cpad, OutPad pd, bf16_raw* out, hipStream_t s, const int* ext) {
+                int cpad, OutPad pd, bf16_raw* out, hipStream_t s, const int* ext,
+                const int* box) {
   if (B <= 0) return;  // bicubic: gridDim.y = images (<= 65535)
   const int ohp = OH + pd.top + pd.bottom, owp = OW + pd.left + pd.right;
-  if (mode == 0 && !ext && g_pre_copy && H == OH && W == OW && cpad == 4 && W % 4 == 0 &&
+  if (mode == 0 && !ext && !box && g_pre_copy && H == OH && W == OW && cpad == 4 && W % 4 == 0 &&
       reinterpret_cast<uintptr_t>(img) % 4 == 0 && (int64_t)B * ohp < (1ll << 30)) {
     hipLaunchKernelGGL(preprocess_copy4_kernel, dim3((B * ohp + 3) / 4), dim3(256), 0, s, img, B,
                        H, W, nrm, pd, out);
@@ -447,9 +481,16 @@ void preprocess(const uint8_t* img, int B, int H, int W, int OH, int OW, Norm3 n
     const int rb = W * 3;
     const uintptr_t ia = (uintptr_t)img;
     const int vec = (rb % 16 == 0 && ia % 16 == 0) ? 16 : (rb % 4 == 0 && ia % 4 == 0) ? 4 : 1;
+    // a box replaces the extent (it lies inside it): the BOX kernels take it in ext's place
 #define PP_LAUNCH(ST, V, CP, L)                                                                 \
-  hipLaunchKernelGGL((preprocess_bilinear_kernel<ST, V, CP>), grid, dim3(256), L, s, img, B, H, \
-                     W, OH, OW, nrm, cpad, pd, out, ext)
+  do {                                                                                          \
+    if (box)                                                                                    \
+      hipLaunchKernelGGL((preprocess_bilinear_kernel<ST, V, CP, true>), grid, dim3(256), L, s,  \
+                         img, B, H, W, OH, OW, nrm, cpad, pd, out, box);                        \
+    else                                                                                        \
+      hipLaunchKernelGGL((preprocess_bilinear_kernel<ST, V, CP>), grid, dim3(256), L, s, img,   \
+                         B, H, W, OH, OW, nrm, cpad, pd, out, ext);                             \
+  } while (0)
 #define PP_CPAD(ST, V, L)                                      \
   do {                                                         \
     if (cpad == 4) PP_LAUNCH(ST, V, 4, L);                     \

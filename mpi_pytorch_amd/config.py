@@ -70,6 +70,10 @@ class Config:
     lr_gamma: float = 0.1                  # step: LR * lr_gamma ^ floor(k / lr_decay_steps)
     lr_decay_steps: int = 0
     clip_grad_norm: float = 0.0            # global-norm gradient clipping (0.0 = off)
+    # input augmentation of the training loader, inside the preprocess launch
+    # (data/augment.py; off by default = the reference's ToTensor -> Resize -> Normalize)
+    augment: str = "none"                  # none | flip | rrc (random-resized crop + flip)
+    aug_scale_min: float = 0.08            # rrc: smallest crop, as a fraction of the image area
     bucket_mb: float = 16.0                # gradient all-reduce bucket size (MiB)
     grad_comm_dtype: str = "fp32"          # fp32 | bf16 (wire dtype of the gradient all-reduce)
     overlap_comm: bool = True              # launch bucket all-reduce during backward
@@ -113,6 +117,10 @@ class Config:
             raise ValueError("lr_schedule=step needs lr_decay_steps > 0 and lr_gamma > 0")
         if not self.clip_grad_norm >= 0.0:
             raise ValueError("clip_grad_norm must be >= 0 (0 = off)")
+        if self.augment not in ("none", "flip", "rrc"):
+            raise ValueError("augment must be none|flip|rrc")
+        if not 0.0 < self.aug_scale_min <= 1.0:
+            raise ValueError("aug_scale_min must be in (0, 1]")
 
     # -----------------------------------------------------------------------------------
     @property
@@ -120,6 +128,14 @@ class Config:
         """True when a schedule, a warm-up or gradient clipping is configured."""
         return (self.lr_schedule != "constant" or self.warmup_steps > 0
                 or self.clip_grad_norm > 0.0)
+
+    @property
+    def augment_spec(self) -> Optional[Dict[str, Any]]:
+        """The training loader's ``augment`` argument (None when augmentation is off).  The
+        seed is the run's, not the rank's: a sample's crop does not depend on the sharding."""
+        if self.augment == "none":
+            return None
+        return dict(kind=self.augment, scale_min=self.aug_scale_min, seed=self.seed)
 
     @property
     def input_hw(self):

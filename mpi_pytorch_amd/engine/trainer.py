@@ -36,6 +36,7 @@ from ..parallel.watchdog import Watchdog
 from ..data.manifest import (read_manifests, synthetic_manifest, SyntheticImages, FolderImages,
                              images_available)
 from ..data.loader import IMAGENET_MEAN, IMAGENET_STD
+from ..data.augment import sample_boxes, sample_ids
 from ..ops import functional as Fn
 from ..parallel import (init_world, get_world, barrier, scatter_object, broadcast_object,
                         all_gather_object,
@@ -52,11 +53,16 @@ class ManifestBatches:
     Host work (synthetic generation or PIL decode) for batch i+1 runs in a worker thread
     while the GPU trains on batch i; images are copied pinned/non-blocking and
     normalised by the GPU preprocess kernel (bilinear resize, no antialias - the
-    reference's ToTensor -> Resize -> Normalize on tensors, main.py:62-65)."""
+    reference's ToTensor -> Resize -> Normalize on tensors, main.py:62-65).
+
+    ``augment`` (training loader only; ``Config.augment_spec``): a dict ``kind`` = "rrc"
+    (random-resized crop + horizontal flip) or "flip", ``scale_min``, ``seed``.  Each batch
+    then carries one crop box and flip bit per image (``data/augment.py``, keyed by the
+    epoch and the file name) into the same preprocess launch."""
 
     def __init__(self, names: Sequence[str], labels: Sequence[int], batch: int, out_hw,
                  device, source, shuffle: bool, seed: int = 0, mode: int = 0, cpad: int = 8,
-                 pad=None):
+                 pad=None, augment=None):
         self.names = list(names)
         self.labels = np.asarray(labels, dtype=np.int64)
         self.batch = batch
@@ -68,6 +74,13 @@ class ManifestBatches:
         self.mode = mode
         self.cpad = cpad
         self.pad = pad
+        self.augment = dict(augment) if augment else None
+        if self.augment is not None:
+            if self.augment.get("kind") not in ("rrc", "flip"):
+                raise ValueError("augment kind must be rrc|flip")
+            if mode != 0:
+                raise ValueError("augment needs mode 0 (the bilinear train transform)")
+            self.ids = sample_ids(self.names)
         self.pool = ThreadPoolExecutor(max_workers=1)
 
     def set_layout(self, spec: dict) -> None:
@@ -88,12 +101,24 @@ class ManifestBatches:
     def _device_synth(self) -> bool:
         return self.device.type == "cuda" and isinstance(self.source, SyntheticImages)
 
-    def _to_device(self, imgs, labels):
+    def _boxes(self, idx, epoch, extents):
+        """Crop boxes of the samples ``idx`` in ``epoch`` (None without augmentation); ``extents``
+        [B, 2] or the (H, W) every image of the batch has."""
+        a = self.augment
+        if a is None:
+            return None
+        ext = np.broadcast_to(np.asarray(extents, dtype=np.int64), (len(idx), 2))
+        return sample_boxes(self.ids[idx], ext, epoch, int(a.get("seed", 0)),
+                            scale=(float(a.get("scale_min", 0.08)), 1.0),
+                            crop=a["kind"] == "rrc")
+
+    def _to_device(self, imgs, labels, idx=None, epoch=0):
         cuda = self.device.type == "cuda"
         if self._device_synth:
             imgs = self.source.load_device(imgs, self.device)
             x = Fn.preprocess(imgs, self.out_hw, IMAGENET_MEAN, IMAGENET_STD, self.mode,
-                              self.cpad, out_dtype=torch.float32, pad=self.pad)
+                              self.cpad, out_dtype=torch.float32, pad=self.pad,
+                              boxes=self._boxes(idx, epoch, imgs.shape[1:3]))
             return x, labels.to(self.device, non_blocking=True)
         ext = None
         if not isinstance(imgs, np.ndarray):
@@ -105,7 +130,9 @@ class ManifestBatches:
         if cuda:
             g = g.pin_memory().to(self.device, non_blocking=True)
         x = Fn.preprocess(g, self.out_hw, IMAGENET_MEAN, IMAGENET_STD, self.mode, self.cpad,
-                          out_dtype=torch.float32, pad=self.pad, extents=ext)
+                          out_dtype=torch.float32, pad=self.pad, extents=ext,
+                          boxes=self._boxes(idx, epoch,
+                                            ext if ext is not None else imgs.shape[1:3]))
         y = labels.to(self.device, non_blocking=cuda)
         return x, y
 
@@ -122,7 +149,7 @@ class ManifestBatches:
             imgs, labels = fut.result()
             if i + 1 < len(chunks):
                 fut = self.pool.submit(self._host, chunks[i + 1])
-            yield self._to_device(imgs, labels)
+            yield self._to_device(imgs, labels, chunks[i], int(e))
 
 
 def _image_source(cfg: Config, names: Sequence[str], src_hw):
@@ -165,7 +192,8 @@ def run_training(cfg: Config) -> dict:
     source = _image_source(cfg, list(my["file_name"].values), src_hw)
     dev = world.device
     train_loader = ManifestBatches(my["file_name"].values, my["category_id"].values,
-                                   cfg.BATCH_SIZE, out_hw, dev, source, True, cfg.seed + rank)
+                                   cfg.BATCH_SIZE, out_hw, dev, source, True, cfg.seed + rank,
+                                   augment=cfg.augment_spec)
     log.info("_Training Dataset Object Created")
     log.info("_Training Loader Created")
     val_loader = None

@@ -1345,7 +1345,7 @@ def count_correct(logits, labels, count: torch.Tensor) -> None:
 
 
 def preprocess(img_u8, out_hw, mean, std, mode: int = 0, cpad: int = 3,
-               out_dtype=torch.bfloat16, pad=None, extents=None):
+               out_dtype=torch.bfloat16, pad=None, extents=None, boxes=None):
     """u8 [B,H,W,3] -> resized, normalized NHWC with ``cpad`` channels, optionally on a
     zero-bordered canvas ``pad`` = (top, bottom, left, right) (the pre-padded input layout
     of a pixel-pair stem, ``models.layers.Conv2d.input_spec``).
@@ -1354,7 +1354,12 @@ def preprocess(img_u8, out_hw, mean, std, mode: int = 0, cpad: int = 3,
     bicubic (the eval transform, evaluation_pipeline.py:89, data/pil_resize.py); mode 2:
     float antialiased bicubic (torch ``F.interpolate(antialias=True)`` semantics).
     ``extents`` (host int [B, 2]): image b occupies rows [0, h_b) and columns [0, w_b) of
-    its slot (real images of different sizes decoded into one padded batch)."""
+    its slot (real images of different sizes decoded into one padded batch).
+    ``boxes`` (host int [B, 5], mode 0): rows (y0, x0, h, w, flip) - image b is resized
+    from that crop of its slot instead of its whole extent (same arithmetic as resizing
+    the contiguous crop) and the result is mirrored along W when flip is 1: random-resized
+    crop + horizontal flip in the same launch (``data/augment.py`` samples the rows).  A
+    box outside its image's extent raises ``ValueError`` here; the kernel does not check."""
     k = K(img_u8)
     pad = list(pad) if pad else []
     if extents is not None:
@@ -1364,6 +1369,8 @@ def preprocess(img_u8, out_hw, mean, std, mode: int = 0, cpad: int = 3,
                 or (extents[:, 1] > Wp).any():
             raise ValueError("preprocess: extents %s do not fit the [%d, %d] slot pitch"
                              % (extents.tolist(), Hp, Wp))
+    if boxes is not None:
+        boxes = _check_boxes(boxes, extents, img_u8.shape, mode)
     if img_u8.is_cuda:
         if mode == 1:  # PIL-exact bicubic (the eval transform)
             tc = _PIL_TABLES.get(img_u8.device)
@@ -1379,10 +1386,41 @@ def preprocess(img_u8, out_hw, mean, std, mode: int = 0, cpad: int = 3,
         ext = None
         if extents is not None:
             ext = torch.from_numpy(extents.astype(np.int32)).to(img_u8.device, non_blocking=True)
+        if boxes is not None:
+            box = torch.from_numpy(boxes).to(img_u8.device, non_blocking=True)
+            return k.preprocess(img_u8, out_hw[0], out_hw[1], list(mean), list(std), mode, cpad,
+                                pad, ext, box=box)
         return k.preprocess(img_u8, out_hw[0], out_hw[1], list(mean), list(std), mode, cpad, pad,
                             ext)
+    if boxes is not None:
+        return k.preprocess(img_u8, out_hw[0], out_hw[1], list(mean), list(std), mode, cpad,
+                            out_dtype, pad, extents, boxes)
     return k.preprocess(img_u8, out_hw[0], out_hw[1], list(mean), list(std), mode, cpad,
                         out_dtype, pad, extents)
+
+
+def _check_boxes(boxes, extents, shape, mode) -> np.ndarray:
+    """Crop boxes (y0, x0, h, w, flip) as a contiguous int32 [B, 5] array, or ``ValueError``:
+    every box must lie inside its image's extent (the slot when ``extents`` is None).  This
+    host check is all that keeps the kernel's reads inside the slot."""
+    if mode != 0:
+        raise ValueError("preprocess: boxes need mode 0 (the bilinear train transform)")
+    B, Hp, Wp = (int(v) for v in shape[:3])
+    bx = np.asarray(boxes)
+    if bx.dtype.kind not in "iu" or bx.ndim != 2 or bx.shape != (B, 5):
+        raise ValueError("preprocess: boxes must be an integer [%d, 5] array, got %s %s"
+                         % (B, bx.dtype, bx.shape))
+    bx = bx.astype(np.int64)
+    eh = extents[:, 0] if extents is not None else np.full(B, Hp, np.int64)
+    ew = extents[:, 1] if extents is not None else np.full(B, Wp, np.int64)
+    y0, x0, h, w, flip = (bx[:, i] for i in range(5))
+    bad = (h < 1) | (w < 1) | (y0 < 0) | (x0 < 0) | (y0 + h > eh) | (x0 + w > ew) \
+        | ((flip != 0) & (flip != 1))
+    if bad.any():
+        b = int(np.argmax(bad))
+        raise ValueError("preprocess: box %s of image %d does not fit its extent (%d, %d) "
+                         "(rows are y0, x0, h, w, flip)" % (bx[b].tolist(), b, eh[b], ew[b]))
+    return np.ascontiguousarray(bx.astype(np.int32))
 
 
 _PIL_TABLES = {}

@@ -688,7 +688,8 @@ def sgd_step_dev(master, grad, buf, shadow, step_t, hyper, momentum, dampening, 
 
 
 # ------------------------------------------------------------------------ preprocessing
-def preprocess(img_u8, oh, ow, mean, std, mode, cpad, out_dtype, pad=None, extents=None):
+def preprocess(img_u8, oh, ow, mean, std, mode, cpad, out_dtype, pad=None, extents=None,
+               boxes=None):
     """u8 NHWC [B,H,W,3] -> normalized NHWC [B,oh,ow,cpad] (zero padded channels), on a
     zero-bordered canvas when pad = (top, bottom, left, right).
 
@@ -698,7 +699,22 @@ def preprocess(img_u8, oh, ow, mean, std, mode, cpad, out_dtype, pad=None, exten
             with PIL.Image.resize
     mode 2: float bicubic with antialias (F.interpolate semantics)
     extents: image b occupies [:h_b, :w_b] of its slot.
+    boxes (mode 0): rows (y0, x0, h, w, flip); image b is the resize of its crop
+    [y0:y0+h, x0:x0+w], mirrored along W when flip is set (RandomResizedCrop ->
+    RandomHorizontalFlip: the mirror of the resize's result, inside the canvas border).
     """
+    if boxes is not None:
+        assert mode == 0, "boxes: mode 0 only"
+        parts = []
+        for b, (y0, x0, h, w, flip) in enumerate(np.asarray(boxes).tolist()):
+            x = preprocess(img_u8[b:b + 1, y0:y0 + h, x0:x0 + w], oh, ow, mean, std, mode, cpad,
+                           out_dtype)
+            parts.append(torch.flip(x, dims=(2,)) if flip else x)
+        x = torch.cat(parts, 0)
+        if pad:
+            t, bo, l, r = pad
+            x = F.pad(x, (0, 0, l, r, t, bo))
+        return x
     if extents is not None:
         parts = [preprocess(img_u8[b:b + 1, :int(h), :int(w)], oh, ow, mean, std, mode, cpad,
                             out_dtype, pad) for b, (h, w) in enumerate(extents)]
