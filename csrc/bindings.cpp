@@ -49,6 +49,13 @@ inline const mpa::bf16_raw* bopt(const Tensor& t) {
   return bp(t);
 }
 
+// A channel window's first element must sit on a 16-byte boundary (a channel offset that
+// is a multiple of 8): the window paths move 8- and 16-byte vectors, and with row strides
+// that are multiples of 8 channels every row then starts aligned too
+inline bool aligned16(const Tensor& t) {
+  return reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0;
+}
+
 inline int vec_width(int64_t c) { return (c % 8 == 0) ? 8 : ((c % 4 == 0) ? 4 : 1); }
 
 float* alloc_ws(Tensor& holder, const Tensor& like, int64_t n) {
@@ -112,6 +119,8 @@ static Tensor conv_fwd_impl(Tensor x, Tensor w, Tensor bias, int64_t sh, int64_t
                     out->stride(1) == (int64_t)Q * out->stride(2) &&
                     out->stride(0) == (int64_t)P * out->stride(1) && out->stride(2) % 8 == 0,
                 "conv_fwd_into: out must be a channel window [N, P, Q, K] of an NHWC buffer");
+    TORCH_CHECK(aligned16(*out),
+                "conv_fwd_into: out must start on a 16-byte boundary (channel offset % 8 == 0)");
     y = *out;
     ldc = (int)out->stride(2);
   } else {
@@ -538,6 +547,8 @@ std::vector<Tensor> bn_bwd_apply(Tensor dy, Tensor x, Tensor y, Tensor mean, Ten
   const int M = x.numel() / C;
   TORCH_CHECK(C % 8 == 0 && sums.numel() == 2 * C && dy.size(-1) == C && lddy % 8 == 0,
               "bn_bwd_apply: shapes");
+  TORCH_CHECK(aligned16(dy),
+              "bn_bwd_apply: dy must start on a 16-byte boundary (channel offset % 8 == 0)");
   const c10::OptionalDeviceGuard g(device_of(x));
   Tensor dx = want_dx ? torch::empty_like(x) : Tensor();
   Tensor gout = want_g ? torch::empty_like(x) : Tensor();
@@ -635,6 +646,7 @@ static void bn_prefix(const Tensor& x, int64_t channels, int* C, int* ldx, int* 
   }
   TORCH_CHECK(*C <= *ldx && *C % 8 == 0 && *ldx % 8 == 0,
               "bn: channels must be a multiple of 8 within the row");
+  TORCH_CHECK(aligned16(x), "bn: x must start on a 16-byte boundary (channel offset % 8 == 0)");
   *M = x.numel() / x.size(-1);
 }
 
@@ -654,6 +666,22 @@ std::vector<Tensor> bn_fwd_train(Tensor x, Tensor stats, Tensor gamma, Tensor be
   int C, ldx, M;
   bn_prefix(x, channels, &C, &ldx, &M);
   const c10::OptionalDeviceGuard g(device_of(x));
+  // out (optional): write y into this bf16 channel window of a wider NHWC buffer (a block
+  // output at the branch's channel offset: concat without a copy); checked before the
+  // statistics pass below launches anything
+  const bool into = out && out->defined() && out->numel() > 0;
+  int ldy = C;
+  if (into) {
+    CHECK_CUDA(*out);
+    CHECK_BF16(*out);
+    TORCH_CHECK(out->sizes() == c10::IntArrayRef(with_last(x, C)) && !has(res) &&
+                    !(mask && mask->defined() && mask->numel()),
+                "bn_fwd_train: out must have the output's shape (no residual / mask)");
+    ldy = row_stride(*out);
+    TORCH_CHECK(ldy % 8 == 0, "bn_fwd_train: out row stride must be a multiple of 8");
+    TORCH_CHECK(aligned16(*out),
+                "bn_fwd_train: out must start on a 16-byte boundary (channel offset % 8 == 0)");
+  }
   Tensor st = stats;
   int lds = C;
   if (has(st)) {
@@ -675,23 +703,7 @@ std::vector<Tensor> bn_fwd_train(Tensor x, Tensor stats, Tensor gamma, Tensor be
     mpa::bn_stats(bp(x), M, C, fopt(rmean), st.data_ptr<float>(), ws.data_ptr<float>(),
                   cur_stream());
   }
-  // out (optional): write y into this bf16 channel window of a wider NHWC buffer (a block
-  // output at the branch's channel offset: concat without a copy)
-  const bool into = out && out->defined() && out->numel() > 0;
-  int ldy = C;
-  Tensor y;
-  if (into) {
-    CHECK_CUDA(*out);
-    CHECK_BF16(*out);
-    TORCH_CHECK(out->sizes() == c10::IntArrayRef(with_last(x, C)) && !has(res) &&
-                    !(mask && mask->defined() && mask->numel()),
-                "bn_fwd_train: out must have the output's shape (no residual / mask)");
-    ldy = row_stride(*out);
-    TORCH_CHECK(ldy % 8 == 0, "bn_fwd_train: out row stride must be a multiple of 8");
-    y = *out;
-  } else {
-    y = torch::empty(with_last(x, C), x.options());
-  }
+  Tensor y = into ? *out : torch::empty(with_last(x, C), x.options());
   if (has(res)) TORCH_CHECK(res.numel() == y.numel(), "bn_fwd_train: residual shape");
   const float* raff = nullptr;
   if (res_affine && res_affine->defined() && res_affine->numel() > 0) {
@@ -795,6 +807,8 @@ std::vector<Tensor> bn_bwd(Tensor dy, Tensor x, Tensor y, Tensor mean, Tensor rs
   const int M = dy.numel() / C;
   TORCH_CHECK(C % 8 == 0 && ldx % 8 == 0 && ldx >= C, "bn: channels must be a multiple of 8");
   TORCH_CHECK(x.numel() / x.size(-1) == M && x.dim() == dy.dim(), "bn_bwd: dy/x shape mismatch");
+  TORCH_CHECK(aligned16(dy) && aligned16(x),
+              "bn_bwd: dy and x must start on a 16-byte boundary (channel offset % 8 == 0)");
   const bool acc = gacc && gacc->defined() && gacc->numel() > 0;
   if (acc) {
     CHECK_CUDA(*gacc);
@@ -814,6 +828,8 @@ std::vector<Tensor> bn_bwd(Tensor dy, Tensor x, Tensor y, Tensor mean, Tensor rs
     TORCH_CHECK(dx_out->sizes() == dy.sizes() && !acc, "bn_bwd: dx_out must have dy's shape");
     lddx = row_stride(*dx_out);
     TORCH_CHECK(lddx % 8 == 0, "bn_bwd: dx_out row stride must be a multiple of 8");
+    TORCH_CHECK(aligned16(*dx_out),
+                "bn_bwd: dx_out must start on a 16-byte boundary (channel offset % 8 == 0)");
   }
   const c10::OptionalDeviceGuard g(device_of(x));
   Tensor dx = (want_dx && !acc)

@@ -876,7 +876,8 @@ def test_linear(gpu, engine, B, Cin, Cout):
 
 
 @pytest.mark.parametrize("M,Cc", [(4096, 64), (1000, 96), (37, 2048), (5000, 24),
-                                  (200000, 64), (70001, 128)])  # last two: 4-row unrolled sweeps
+                                  (200000, 64), (70001, 128),  # these two: 4-row unrolled sweeps
+                                  (64, 2056)])  # C > 2048: a second block row (gridDim.y = 2)
 @pytest.mark.parametrize("relu,res", [(True, True), (False, False), (True, False)])
 def test_bn(gpu, M, Cc, relu, res):
     torch.manual_seed(4)
@@ -1352,7 +1353,8 @@ def test_cross_entropy_padded_rows(gpu):
     assert int(cnt) == B
 
 
-@pytest.mark.parametrize("B,NC", [(128, 64500), (7, 1000), (5, 33)])
+@pytest.mark.parametrize("B,NC", [(128, 64500), (7, 1000), (5, 33),
+                                  (300, 1000), (300, 33)])  # B > 256: the loss sum strides rows
 def test_cross_entropy(gpu, B, NC):
     logits = bf(B, NC, dev=gpu, scale=3.0)
     labels = torch.randint(0, NC, (B,), device=gpu)
@@ -1741,3 +1743,448 @@ def test_stem_pool_forward_oracle(gpu, N, HW):
                                                  False, cnt, zsel_out=zsel)
     gi = _global_idx(idx, P, P, 3, 3, 2, 2, 1, 1)
     _stem_pool_oracle_checks(z, y, gi, zsel, g, rm, rv, cnt, idx=idx)
+
+
+# --------------------------------------------------------------------------------------
+# Stores into a channel window of a wider buffer (row stride != channel count: DenseNet's
+# and Inception's concat-free block outputs) and the small kernels.  The checks below take
+# the implementation under test as `impl`: the native extension on the GPU here, and `ref`
+# itself on the CPU in tests/test_kernel_inventory_cpu.py, which shows that the oracle alone
+# meets every bound and sentinel condition.
+
+def sentinel_window(lead, ld, off, width, dtype, dev):
+    """A [*lead, ld] buffer of random sentinels and its channel window [..., off:off+width]
+    (a view).  Take the pristine copy after filling the window, where a test fills it."""
+    buf = torch.randn(*lead, ld, device=dev).to(dtype)
+    return buf, buf[..., off:off + width]
+
+
+def neighbours_untouched(buf, buf0, off, width):
+    """Every element of buf outside the channel window still equals its sentinel."""
+    return (torch.equal(buf[..., :off], buf0[..., :off])
+            and torch.equal(buf[..., off + width:], buf0[..., off + width:]))
+
+
+WINDOW_CONV_CASES = [
+    # (N, H, W, C, K, R, S, stride, pad), ld, off, pinned
+    # pinned: the contiguous conv_fwd of this shape splits K on some engine (rows_plan /
+    # choose_splits: fewer than 256 tiles and >= 16 K-tiles of 32, i.e. R*S*C >= 512), which
+    # the window call may not (split-K's finalize writes dense rows); the bitwise comparison
+    # pins that call to one split with igemm_force_tile(0, 0, 1).  The other four cases
+    # (1x1/s2: K 64; 5x5 C 12: 300; C 3: 27; 7x1 C 40: 280) never split.
+    ((2, 28, 28, 128, 32, 3, 3, 1, 1), 256, 64, True),     # DenseNet growth conv: halo NJ = 2
+    ((3, 7, 7, 128, 32, 3, 3, 1, 1), 96, 64, True),        # window ends at the row end
+    ((2, 56, 56, 64, 64, 3, 3, 1, 1), 192, 64, True),      # resident weights, 448-pixel tiles
+    ((2, 7, 7, 512, 64, 3, 3, 1, 1), 128, 0, True),        # deep K, small M
+    ((2, 14, 14, 64, 128, 1, 1, 2, 0), 256, 128, False),   # 1x1/s2
+    ((2, 17, 17, 64, 200, 3, 3, 2, 0), 264, 32, True),     # K not a tile multiple: column tail
+    ((1, 13, 13, 12, 20, 5, 5, 1, 2), 32, 8, False),       # scalar gather, K % 8 != 0
+    ((8, 40, 40, 3, 5, 3, 3, 1, 1), 8, 0, False),          # K = 5: per-element column tail
+    ((2, 17, 17, 48, 64, 5, 5, 1, 2), 160, 96, True),      # padded-K uniform taps
+    ((2, 12, 12, 40, 24, 7, 1, 1, (3, 0)), 64, 40, False),  # 32-wide tile, window at row end
+    ((2, 33, 150, 64, 128, 3, 3, 1, 1), 256, 64, True),    # strip tiles, two column tiles
+    ((1, 20, 131, 96, 32, 3, 3, 1, 1), 64, 32, True),      # strip tiles, 32-wide output
+]
+# bias + ReLU + statistics runs every shape on the implicit-GEMM engines (the halo kernels
+# do not instantiate that epilogue); shifted statistics alone is DenseNet's growth conv and
+# the flavour that reaches the halo and strip kernels' window stores under "dma-halo"
+WINDOW_CONV_FLAVOURS = [(True, True), (False, False)]  # (bias, relu); statistics always
+
+
+def check_conv_window(impl, dev, geom, ld, off, bias, relu):
+    """conv_fwd_into a channel window of a sentinel buffer, statistics into a row-window of
+    a sentinel table: the window and its statistics match the oracle within test_conv_fwd's
+    bounds, and nothing outside either window changed.  Returns the inputs and the window
+    for conv_window_same_as_contiguous."""
+    torch.manual_seed(40)
+    N, H, W, Cc, K, R, S, st, pd = geom
+    ph, pw = _pair(pd)
+    P, Q = ref.conv_out_hw(H, W, R, S, st, st, ph, pw)
+    x = bf(N, H, W, Cc, dev=dev)
+    w = bf(K, R, S, Cc, dev=dev, scale=1.0 / math.sqrt(R * S * Cc))
+    b = torch.randn(K, device=dev) if bias else torch.empty(0, device=dev)
+    shift = torch.randn(K, device=dev) * 0.1
+    buf, win = sentinel_window((N, P, Q), ld, off, K, torch.bfloat16, dev)
+    tab, stw = sentinel_window((2,), ld, off, K, torch.float32, dev)
+    buf0, tab0 = buf.clone(), tab.clone()
+    impl.conv_fwd_into(x, w, b, st, st, ph, pw, relu, stw, shift, win)
+    st_r = torch.zeros(2, K, device=dev)
+    yr = ref.conv_fwd(x, w, b, st, st, ph, pw, relu, st_r, shift)
+    assert win.shape == yr.shape
+    print("conv window", geom, ld, off, bias, relu, "y", rel(win, yr), "stats", rel(stw, st_r))
+    assert rel(win, yr) < 2e-2
+    assert rel(stw, st_r) < 2e-2
+    assert neighbours_untouched(buf, buf0, off, K)
+    assert neighbours_untouched(tab, tab0, off, K)
+    return (x, w, b, st, st, ph, pw, relu, shift), win
+
+
+def conv_window_same_as_contiguous(impl, dev, inputs, win):
+    """The window holds, bit for bit, what conv_fwd of the same inputs returns (same tile,
+    same K order, one split on both sides)."""
+    x, w, b, sh, sw, ph, pw, relu, shift = inputs
+    y = impl.conv_fwd(x, w, b, sh, sw, ph, pw, relu, torch.zeros(2, w.shape[0], device=dev),
+                      shift)
+    assert torch.equal(win, y), rel(win, y)
+
+
+@pytest.mark.parametrize("case", WINDOW_CONV_CASES)
+def test_conv_fwd_into_window(gpu, engine, case):
+    """conv_fwd_into (ldc != N) on every engine: oracle, untouched neighbours, and the
+    contiguous call's bits (static plans on both sides: tuner off)."""
+    geom, ld, off, pinned = case
+    C().igemm_set_tune(0)
+    try:
+        for bias, relu in WINDOW_CONV_FLAVOURS:
+            inputs, win = check_conv_window(C(), gpu, geom, ld, off, bias, relu)
+            if pinned:
+                C().igemm_force_tile(0, 0, 1)
+            try:
+                conv_window_same_as_contiguous(C(), gpu, inputs, win)
+            finally:
+                C().igemm_force_tile(0, 0, 0)
+    finally:
+        C().igemm_set_tune(1)
+
+
+def test_conv_fwd_into_window_tuned(gpu, engine):
+    """The first case with the tile autotuner at its default and nothing cached: its timed
+    scratch launches (scratch sized with max(ldc, N)) leave the neighbours untouched too."""
+    geom, ld, off, _ = WINDOW_CONV_CASES[0]
+    saved = C().igemm_tuned_table()
+    C().igemm_tuned_load("", True)  # forget every tuned tile: this shape tunes again
+    try:
+        for bias, relu in WINDOW_CONV_FLAVOURS:
+            check_conv_window(C(), gpu, geom, ld, off, bias, relu)
+        torch.cuda.synchronize()
+    finally:
+        C().igemm_tuned_load(saved, False)
+
+
+BN_WINDOW_CASES = [
+    # M, C, ld, off
+    (1003, 24, 64, 40),
+    (4096, 64, 192, 64),
+    (37, 136, 272, 136),
+    (64, 2056, 4112, 2056),   # C > 2048: two block rows
+]
+# exactly 40 * 2^20 elements: the nontemporal loads and stores (stream_hint); ~105 MB a buffer
+BN_WINDOW_STREAM = (163840, 256, 320, 64)
+
+
+def _bn_inputs(M, Cc, ld, off, dev):
+    """x contiguous and the same values as a channel window of a sentinel buffer."""
+    xc = (bf(M, Cc, dev=dev, scale=2.0) + 0.5).to(torch.bfloat16)
+    xbuf, xw = sentinel_window((M,), ld, off, Cc, torch.bfloat16, dev)
+    xw.copy_(xc)
+    g = torch.rand(Cc, device=dev) + 0.5
+    b = torch.randn(Cc, device=dev)
+    return xc, xbuf, xw, g, b
+
+
+def check_bn_fwd_window(impl, dev, M, Cc, ld, off, relu, x_window):
+    """bn_fwd_train(out= a window of a sentinel buffer, stats= a row-window of a [2, ld]
+    table, x contiguous or a window view) == the same call on contiguous copies bit for bit
+    (the grid depends on (M, C) only), == the oracle within test_bn's bounds; neighbours, the
+    table and x unchanged."""
+    torch.manual_seed(41)
+    e = torch.empty(0, device=dev)
+    xc, xbuf, xw, g, b = _bn_inputs(M, Cc, ld, off, dev)
+    xbuf0, xc0 = xbuf.clone(), xc.clone()
+    S = impl.bn_stats(xc, e)
+    tab, tw = sentinel_window((2,), ld, off, Cc, torch.float32, dev)
+    tw.copy_(S)
+    tab0 = tab.clone()
+    obuf, ow = sentinel_window((M,), ld, off, Cc, torch.bfloat16, dev)
+    obuf0 = obuf.clone()
+    rm, rv = torch.zeros(Cc, device=dev), torch.ones(Cc, device=dev)
+    rm2, rv2, rm3, rv3 = rm.clone(), rv.clone(), rm.clone(), rv.clone()
+    y, mean, rstd = impl.bn_fwd_train(xw if x_window else xc, tw, g, b, rm, rv, 0.1, 1e-5, e,
+                                      relu, out=ow)
+    y2, mean2, rstd2 = impl.bn_fwd_train(xc, S, g, b, rm2, rv2, 0.1, 1e-5, e, relu)
+    yr, meanr, rstdr = ref.bn_fwd_train(xc, e, g, b, rm3, rv3, 0.1, 1e-5, e, relu)
+    assert y.data_ptr() == ow.data_ptr() and y.shape == y2.shape
+    assert torch.equal(ow, y2)
+    assert torch.equal(mean, mean2) and torch.equal(rstd, rstd2)
+    assert torch.equal(rm, rm2) and torch.equal(rv, rv2)
+    print("bn fwd window", (M, Cc, ld, off), relu, x_window, rel(ow, yr), rel(mean, meanr),
+          rel(rstd, rstdr), rel(rm, rm3), rel(rv, rv3))
+    assert rel(ow, yr) < 2e-2
+    assert rel(mean, meanr) < 1e-3 and rel(rstd, rstdr) < 1e-3
+    assert rel(rm, rm3) < 1e-3 and rel(rv, rv3) < 1e-3
+    assert neighbours_untouched(obuf, obuf0, off, Cc)
+    assert torch.equal(tab, tab0) and torch.equal(xbuf, xbuf0) and torch.equal(xc, xc0)
+
+
+def check_bn_bwd_window(impl, dev, M, Cc, ld, off):
+    """bn_bwd with dy a window of a wider gradient buffer, x a window view and dx_out a
+    window of a sentinel buffer, for the three ReLU mask sources (y, the forward's bit mask,
+    recomputed from x with beta): dx, g, dgamma, dbeta == the contiguous call bit for bit,
+    == the oracle within test_bn's bounds (one oracle, masked by the same y: the three
+    sources describe the same mask), dx_out's neighbours and the inputs unchanged."""
+    torch.manual_seed(42)
+    e = torch.empty(0, device=dev)
+    xc, xbuf, xw, g, b = _bn_inputs(M, Cc, ld, off, dev)
+    rm, rv = torch.zeros(Cc, device=dev), torch.ones(Cc, device=dev)
+    y, mean, rstd = impl.bn_fwd_train(xc, e, g, b, rm, rv, 0.1, 1e-5, e, True)
+    ymask = ref.relu_bitmask(y)
+    dyc = bf(M, Cc, dev=dev)
+    dybuf, dyw = sentinel_window((M,), ld, off, Cc, torch.bfloat16, dev)
+    dyw.copy_(dyc)
+    xbuf0, dybuf0 = xbuf.clone(), dybuf.clone()
+    dgr, dbr = torch.zeros(Cc, device=dev), torch.zeros(Cc, device=dev)
+    dxr, ggr = ref.bn_bwd(dyc, xc, y, mean, rstd, g, dgr, dbr, True)
+    for src, yy, zb, ym in (("y", y, None, None), ("ymask", e, None, ymask),
+                            ("zmask_beta", e, b, None)):
+        dxbuf, dxw = sentinel_window((M,), ld, off, Cc, torch.bfloat16, dev)
+        dxbuf0 = dxbuf.clone()
+        dg, db = torch.zeros(Cc, device=dev), torch.zeros(Cc, device=dev)
+        dg2, db2 = dg.clone(), db.clone()
+        dx, gg = impl.bn_bwd(dyw, xw, yy, mean, rstd, g, dg, db, True, True, zmask_beta=zb,
+                             ymask=ym, dx_out=dxw)
+        dx2, gg2 = impl.bn_bwd(dyc, xc, yy, mean, rstd, g, dg2, db2, True, True, zmask_beta=zb,
+                               ymask=ym)
+        assert dx.data_ptr() == dxw.data_ptr(), src
+        assert torch.equal(dxw, dx2) and torch.equal(gg, gg2), src
+        assert torch.equal(dg, dg2) and torch.equal(db, db2), src
+        print("bn bwd window", (M, Cc, ld, off), src, rel(dxw, dxr), rel(gg, ggr), rel(dg, dgr),
+              rel(db, dbr))
+        assert rel(dxw, dxr) < 3e-2, src
+        assert rel(gg, ggr) < 2e-2, src
+        assert rel(dg, dgr) < 1e-2 and rel(db, dbr) < 1e-2, src
+        assert neighbours_untouched(dxbuf, dxbuf0, off, Cc), src
+    assert torch.equal(xbuf, xbuf0) and torch.equal(dybuf, dybuf0)
+
+
+def check_bn_bwd_apply_window(impl, dev, M, Cc, ld, off):
+    """bn_bwd_apply (the apply pass with precomputed sums) reading dy from a window == the
+    contiguous call bit for bit, == the oracle within test_bn's bounds."""
+    torch.manual_seed(43)
+    e = torch.empty(0, device=dev)
+    xc, _, _, g, b = _bn_inputs(M, Cc, ld, off, dev)
+    rm, rv = torch.zeros(Cc, device=dev), torch.ones(Cc, device=dev)
+    y, mean, rstd = impl.bn_fwd_train(xc, e, g, b, rm, rv, 0.1, 1e-5, e, True)
+    dyc = bf(M, Cc, dev=dev)
+    dybuf, dyw = sentinel_window((M,), ld, off, Cc, torch.bfloat16, dev)
+    dyw.copy_(dyc)
+    dybuf0 = dybuf.clone()
+    gf = dyc.float() * (y.float() > 0)
+    sums = torch.cat([gf.sum(0), (gf * ((xc.float() - mean) * rstd)).sum(0)]).contiguous()
+    acc = [torch.zeros(Cc, device=dev) for _ in range(6)]
+    dx, gg = impl.bn_bwd_apply(dyw, xc, y, mean, rstd, g, acc[0], acc[1], sums, True, True)
+    dx2, gg2 = impl.bn_bwd_apply(dyc, xc, y, mean, rstd, g, acc[2], acc[3], sums, True, True)
+    dxr, ggr = ref.bn_bwd_apply(dyc, xc, y, mean, rstd, g, acc[4], acc[5], sums, True, True)
+    assert torch.equal(dx, dx2) and torch.equal(gg, gg2)
+    assert torch.equal(acc[0], acc[2]) and torch.equal(acc[1], acc[3])
+    print("bn bwd apply window", rel(dx, dxr), rel(gg, ggr), rel(acc[0], acc[4]),
+          rel(acc[1], acc[5]))
+    assert rel(dx, dxr) < 3e-2 and rel(gg, ggr) < 2e-2
+    assert rel(acc[0], acc[4]) < 1e-2 and rel(acc[1], acc[5]) < 1e-2
+    assert torch.equal(dybuf, dybuf0)
+
+
+@pytest.mark.parametrize("case", BN_WINDOW_CASES + [BN_WINDOW_STREAM])
+@pytest.mark.parametrize("relu", [True, False])
+@pytest.mark.parametrize("x_window", [False, True])
+def test_bn_fwd_train_window(gpu, case, relu, x_window):
+    check_bn_fwd_window(C(), gpu, *case, relu, x_window)
+
+
+@pytest.mark.parametrize("case", BN_WINDOW_CASES + [BN_WINDOW_STREAM])
+def test_bn_bwd_window(gpu, case):
+    # (a two-block slab combine adds two partials to zero with atomics: a + b == b + a, so
+    # the sums - and with them dx - are the same bits in either order)
+    check_bn_bwd_window(C(), gpu, *case)
+
+
+def test_bn_bwd_apply_window(gpu):
+    check_bn_bwd_apply_window(C(), gpu, *BN_WINDOW_CASES[1])
+
+
+def test_window_base_alignment(gpu):
+    """A window whose first element is not on a 16-byte boundary (channel offset 4, strides
+    still multiples of 8) is rejected by the binding, before anything is launched: the
+    window paths use 8- and 16-byte vector accesses."""
+    e = torch.empty(0, device=gpu)
+    M, Cc, ld = 64, 32, 64
+    x = bf(1, 8, 8, 32, dev=gpu)
+    w = bf(32, 3, 3, 32, dev=gpu, scale=0.1)
+    buf, win = sentinel_window((1, 8, 8), ld, 4, 32, torch.bfloat16, gpu)
+    buf0 = buf.clone()
+    with pytest.raises(RuntimeError, match="16-byte"):
+        C().conv_fwd_into(x, w, e, 1, 1, 1, 1, False, e, e, win)
+    xc, g, b = bf(M, Cc, dev=gpu), torch.ones(Cc, device=gpu), torch.zeros(Cc, device=gpu)
+    mean, rstd = torch.zeros(Cc, device=gpu), torch.ones(Cc, device=gpu)
+    obuf, ow = sentinel_window((M,), ld, 4, Cc, torch.bfloat16, gpu)
+    obuf0 = obuf.clone()
+    rm, rv = torch.zeros(Cc, device=gpu), torch.ones(Cc, device=gpu)
+    with pytest.raises(RuntimeError, match="16-byte"):  # (no stats given: checked before bn_stats)
+        C().bn_fwd_train(xc, e, g, b, rm, rv, 0.1, 1e-5, e, True, out=ow)
+    with pytest.raises(RuntimeError, match="16-byte"):
+        C().bn_fwd_train(ow, torch.zeros(2, Cc, device=gpu), g, b, rm, rv, 0.1, 1e-5, e, True)
+    dg, db = torch.zeros(Cc, device=gpu), torch.zeros(Cc, device=gpu)
+    for dy, xx, dxo in ((ow, xc, None), (xc, ow, None), (xc, xc, ow)):
+        with pytest.raises(RuntimeError, match="16-byte"):
+            C().bn_bwd(dy, xx, e, mean, rstd, g, dg, db, True, False, dx_out=dxo)
+    with pytest.raises(RuntimeError, match="16-byte"):
+        C().bn_bwd_apply(ow, xc, e, mean, rstd, g, dg, db, torch.zeros(2 * Cc, device=gpu),
+                         True, False)
+    torch.cuda.synchronize()
+    assert torch.equal(buf, buf0) and torch.equal(obuf, obuf0)
+    assert not dg.any() and not db.any() and not rm.any() and bool((rv == 1).all())
+
+
+# ------------------------------------------------------------------- the small kernels
+CHAN_CASES = [(105, 32, 96, 64), (1003, 8, 8, 0), (4096, 136, 264, 128)]  # pixels, cs, ctot, off
+
+
+def check_chan_accum(impl, dev, pixels, cs, ctot, off, assign):
+    """fp32 G[..., off:off+cs] (+)= bf16 src: exactly the oracle (the bf16 converts exactly
+    and one fp32 add rounds once); the other columns of G unchanged."""
+    torch.manual_seed(45)
+    G = torch.randn(pixels, ctot, device=dev)
+    G0, Gr = G.clone(), G.clone()
+    src = bf(pixels, cs, dev=dev)
+    impl.chan_accum(G, off, src, assign)
+    ref.chan_accum(Gr, off, src, assign)
+    assert torch.equal(G, Gr)
+    assert neighbours_untouched(G, G0, off, cs)
+    assert not torch.equal(G[:, off:off + cs], G0[:, off:off + cs])
+
+
+def check_chan_extract(impl, dev, pixels, cs, ctot, off, act_dtype):
+    """The bf16 copy of fp32 G[..., off:off+cs] rounds to nearest even: half of the inputs
+    have the low 16 bits 0x8000 (exact ties), with both parities of the kept mantissa bit.
+    act_dtype: the activation dtype of `impl` (bf16 native; the oracle's CPU path keeps
+    fp32 and is rounded here)."""
+    torch.manual_seed(46)
+    bits = torch.randn(pixels, ctot, device=dev).view(torch.int32)
+    tie = torch.rand(pixels, ctot, device=dev) < 0.5
+    bits = torch.where(tie, (bits & -65536) | 0x8000, bits)
+    G = bits.view(torch.float32).contiguous()
+    G0 = G.clone()
+    kept = ((bits >> 16) & 1)[:, off:off + cs][tie[:, off:off + cs]]
+    assert bool((kept == 0).any()) and bool((kept == 1).any())
+    out = impl.chan_extract(G, off, cs)
+    assert out.dtype == act_dtype and out.shape == (pixels, cs)
+    assert torch.equal(out.to(torch.bfloat16), G0[:, off:off + cs].to(torch.bfloat16))
+    assert torch.equal(G, G0)
+
+
+def check_add_f32(impl, dev, n):
+    torch.manual_seed(47)
+    dst, src = torch.randn(n, device=dev), torch.randn(n, device=dev)
+    want, src0 = dst.clone(), src.clone()
+    ref.add_f32_(want, src)
+    impl.add_f32_(dst, src)
+    assert torch.equal(dst, want) and torch.equal(src, src0)
+
+
+def check_zero_f32(impl, dev, n):
+    t = torch.randn(n, device=dev)
+    want = t.clone()
+    ref.zero_f32(want)
+    impl.zero_f32(t)
+    assert torch.equal(t, want) and not t.any()
+
+
+def check_step_inc(impl, dev):
+    step, want = torch.full((1,), 41.0, device=dev), torch.full((1,), 41.0, device=dev)
+    for _ in range(3):
+        impl.step_inc(step)
+        ref.step_inc(want)
+    assert torch.equal(step, want) and float(step) == 44.0
+
+
+def check_relu_fwd(impl, dev, n):
+    torch.manual_seed(48)
+    x = bf(n, dev=dev)
+    x0 = x.clone()
+    y = impl.relu_fwd(x)
+    assert y.dtype == x.dtype and torch.equal(y, ref.relu_fwd(x0)) and torch.equal(x, x0)
+    if n >= 64:  # (both branches taken)
+        assert bool((y == 0).any()) and bool((y > 0).any())
+
+
+def affine_act_bound(x, aff, want):
+    """|a - b| <= 2^-7 |b| + 2^-23 (|x sc| + |sh|), in float64: one bf16 step (the kernel
+    may fuse the multiply-add, the oracle rounds the product and the sum), plus the fp32
+    rounding of the product."""
+    xs = (x.double() * aff[0].double()).abs()
+    return 2.0 ** -7 * want.double().abs() + 2.0 ** -23 * (xs + aff[1].double().abs())
+
+
+def check_affine_act(impl, dev, M, Cc, relu):
+    torch.manual_seed(49)
+    x = bf(M, Cc, dev=dev, scale=2.0).clamp(-8, 8)
+    aff = torch.stack([torch.rand(Cc, device=dev) + 0.5, torch.randn(Cc, device=dev)])
+    assert float((x.float() * aff[0]).abs().max()) <= 16.0
+    y = impl.affine_act(x, aff, relu)
+    want = ref.affine_act(x, aff, relu)
+    assert y.dtype == x.dtype and y.shape == x.shape
+    err = (y.double() - want.double()).abs()
+    bound = affine_act_bound(x, aff, want)
+    print("affine_act", (M, Cc), relu, float((err / bound.clamp_min(1e-30)).max()))
+    assert bool((err <= bound).all())
+    if relu:
+        assert bool((y >= 0).all()) and bool((y == 0).any())
+
+
+def check_ce_fwd_weighted(impl, dev, B, NC):
+    """Two heads summed into one loss (Inception's main + 0.4 * aux): the first call
+    assigns out, the second (other logits) accumulates; both add to the running acc.
+    out, acc and the returned lse against the oracle at test_cross_entropy's bounds."""
+    torch.manual_seed(50)
+    out, acc = torch.full((1,), 123.0, device=dev), torch.full((1,), 5.0, device=dev)
+    outr, accr = out.clone(), acc.clone()
+    for accumulate in (False, True):
+        logits = bf(B, NC, dev=dev, scale=3.0)
+        labels = torch.randint(0, NC, (B,), device=dev)
+        lse = impl.ce_fwd_weighted(logits, labels, out, acc, 0.4, accumulate)
+        lser = ref.ce_fwd_weighted(logits, labels, outr, accr, 0.4, accumulate)
+        print("ce_fwd_weighted", (B, NC), accumulate, float(out), float(outr), float(acc),
+              float(accr), rel(lse, lser))
+        assert abs(float(out) - float(outr)) < 1e-3 * max(1.0, abs(float(outr)))
+        assert abs(float(acc) - float(accr)) < 1e-3 * max(1.0, abs(float(accr)))
+        assert rel(lse, lser) < 1e-4
+
+
+@pytest.mark.parametrize("case", CHAN_CASES)
+@pytest.mark.parametrize("assign", [True, False])
+def test_chan_accum(gpu, case, assign):
+    check_chan_accum(C(), gpu, *case, assign)
+
+
+@pytest.mark.parametrize("case", CHAN_CASES)
+def test_chan_extract(gpu, case):
+    check_chan_extract(C(), gpu, *case, torch.bfloat16)
+
+
+@pytest.mark.parametrize("n", [1, 7, 4099])
+def test_add_f32(gpu, n):
+    check_add_f32(C(), gpu, n)
+
+
+@pytest.mark.parametrize("n", [4, 4100])
+def test_zero_f32(gpu, n):
+    check_zero_f32(C(), gpu, n)
+
+
+def test_step_inc(gpu):
+    check_step_inc(C(), gpu)
+
+
+@pytest.mark.parametrize("n", [8, 8 * 1003])
+def test_relu_fwd(gpu, n):
+    check_relu_fwd(C(), gpu, n)
+
+
+@pytest.mark.parametrize("M,Cc", [(1003, 24), (37, 136)])
+@pytest.mark.parametrize("relu", [True, False])
+def test_affine_act(gpu, M, Cc, relu):
+    check_affine_act(C(), gpu, M, Cc, relu)
+
+
+@pytest.mark.parametrize("NC", [1000, 33])  # 16-B rows: the padded kernel; 33: the scalar one
+def test_ce_fwd_weighted(gpu, NC):
+    check_ce_fwd_weighted(C(), gpu, 300, NC)
