@@ -1256,8 +1256,15 @@ static int logits_ld(const Tensor& logits) {
   return (int)logits.stride(0);
 }
 
-std::vector<Tensor> ce_fwd(Tensor logits, Tensor labels) {
+static float check_smoothing(double smoothing) {
+  TORCH_CHECK(smoothing >= 0.0 && smoothing <= 1.0, "label smoothing must be in [0, 1], got ",
+              smoothing);
+  return (float)smoothing;
+}
+
+std::vector<Tensor> ce_fwd(Tensor logits, Tensor labels, double smoothing) {
   const int ld = logits_ld(logits);
+  const float eps = check_smoothing(smoothing);
   CHECK_CUDA(labels);
   TORCH_CHECK(labels.scalar_type() == torch::kInt64, "labels must be int64");
   const int B = logits.size(0), NC = logits.size(1);
@@ -1265,7 +1272,7 @@ std::vector<Tensor> ce_fwd(Tensor logits, Tensor labels) {
   Tensor buf = torch::empty({1 + B}, logits.options().dtype(torch::kFloat32));
   Tensor lse = torch::empty({B}, logits.options().dtype(torch::kFloat32));
   mpa::ce_fwd(bp(logits), labels.contiguous().data_ptr<int64_t>(), B, NC, ld,
-              buf.data_ptr<float>(), lse.data_ptr<float>(), cur_stream());
+              buf.data_ptr<float>(), lse.data_ptr<float>(), cur_stream(), eps);
   return {buf.narrow(0, 0, 1), lse};
 }
 
@@ -1274,8 +1281,9 @@ std::vector<Tensor> ce_fwd(Tensor logits, Tensor labels) {
 // out[0] = (or +=, accumulate) weight * mean CE and acc[0] += the same (acc optional);
 // returns the per-row log-sum-exp for the backward
 Tensor ce_fwd_weighted(Tensor logits, Tensor labels, Tensor out, Tensor acc, double weight,
-                       bool accumulate) {
+                       bool accumulate, double smoothing) {
   const int ld = logits_ld(logits);
+  const float eps = check_smoothing(smoothing);
   CHECK_CUDA(labels);
   TORCH_CHECK(labels.scalar_type() == torch::kInt64, "labels must be int64");
   CHECK_CUDA(out);
@@ -1288,17 +1296,19 @@ Tensor ce_fwd_weighted(Tensor logits, Tensor labels, Tensor out, Tensor acc, dou
   Tensor lse = torch::empty({B}, logits.options().dtype(torch::kFloat32));
   mpa::ce_fwd_weighted(bp(logits), labels.contiguous().data_ptr<int64_t>(), B, NC, ld,
                        out.data_ptr<float>(), fopt_mut(acc), (float)weight, accumulate,
-                       rows.data_ptr<float>(), lse.data_ptr<float>(), cur_stream());
+                       rows.data_ptr<float>(), lse.data_ptr<float>(), cur_stream(), eps);
   return lse;
 }
 
-Tensor ce_bwd(Tensor logits, Tensor labels, Tensor lse, Tensor grad_out, double weight) {
+Tensor ce_bwd(Tensor logits, Tensor labels, Tensor lse, Tensor grad_out, double weight,
+              double smoothing) {
   const int ld = logits_ld(logits);
+  const float eps = check_smoothing(smoothing);
   const int B = logits.size(0), NC = logits.size(1);
   const c10::OptionalDeviceGuard g(device_of(logits));
   Tensor d = torch::empty({B, ld}, logits.options());
   mpa::ce_bwd(bp(logits), labels.contiguous().data_ptr<int64_t>(), fopt(lse), fopt(grad_out), B,
-              NC, ld, bpm(d), cur_stream(), (float)weight);
+              NC, ld, bpm(d), cur_stream(), (float)weight, eps);
   return ld == NC ? d : d.narrow(1, 0, NC);
 }
 
@@ -1308,6 +1318,22 @@ void argmax_correct(Tensor logits, Tensor labels, Tensor count) {
   const c10::OptionalDeviceGuard g(device_of(logits));
   mpa::argmax_correct(bp(logits), labels.contiguous().data_ptr<int64_t>(), logits.size(0),
                       logits.size(1), ld, count.data_ptr<int64_t>(), cur_stream());
+}
+
+// count += #{rows whose label is among the k largest logits}, ties to the lower index
+void topk_correct(Tensor logits, Tensor labels, int64_t k, Tensor count) {
+  const int ld = logits_ld(logits);
+  CHECK_CUDA(labels);
+  CHECK_CUDA(count);
+  TORCH_CHECK(labels.scalar_type() == torch::kInt64 && labels.numel() == logits.size(0),
+              "topk_correct: one int64 label per row");
+  TORCH_CHECK(count.scalar_type() == torch::kInt64 && count.numel() >= 1,
+              "count must be int64");
+  TORCH_CHECK(k >= 1, "topk_correct: k must be >= 1, got ", k);
+  const c10::OptionalDeviceGuard g(device_of(logits));
+  mpa::topk_correct(bp(logits), labels.contiguous().data_ptr<int64_t>(), logits.size(0),
+                    logits.size(1), ld, (int)std::min<int64_t>(k, INT32_MAX),
+                    count.data_ptr<int64_t>(), cur_stream());
 }
 
 // ----------------------------------------------------------------------------- optim
@@ -1852,11 +1878,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("linear_dgrad", &linear_dgrad, py::arg("dy"), py::arg("w"), py::arg("wt") = py::none());
   m.def("linear_wgrad", &linear_wgrad, py::arg("dy"), py::arg("x"), py::arg("dw"),
         py::arg("overwrite") = false);
-  m.def("ce_fwd", &ce_fwd);
+  m.def("ce_fwd", &ce_fwd, py::arg("logits"), py::arg("labels"), py::arg("smoothing") = 0.0);
   m.def("ce_bwd", &ce_bwd, py::arg("logits"), py::arg("labels"), py::arg("lse"),
-        py::arg("grad_out"), py::arg("weight") = 1.0);
-  m.def("ce_fwd_weighted", &ce_fwd_weighted);
+        py::arg("grad_out"), py::arg("weight") = 1.0, py::arg("smoothing") = 0.0);
+  m.def("ce_fwd_weighted", &ce_fwd_weighted, py::arg("logits"), py::arg("labels"),
+        py::arg("out"), py::arg("acc"), py::arg("weight"), py::arg("accumulate"),
+        py::arg("smoothing") = 0.0);
   m.def("argmax_correct", &argmax_correct);
+  m.def("topk_correct", &topk_correct, py::arg("logits"), py::arg("labels"), py::arg("k"),
+        py::arg("count"));
   m.def("adam_step", &adam_step);
   m.def("sgd_step", &sgd_step);
   m.def("grad_sqnorm", &grad_sqnorm,

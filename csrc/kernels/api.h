@@ -369,18 +369,19 @@ void split_channels(const bf16_raw* dy, const int* chans, int nseg, int pixels, 
 
 // loss.hip
 // logits rows have stride ld >= NC (padded heads); ce_bwd writes dlogits with stride ld and
-// zeros in columns NC..ld-1
+// zeros in columns NC..ld-1.  smoothing: torch's label_smoothing in [0, 1]; 0 runs the plain
+// kernels.
 void ce_fwd_rows(const bf16_raw* logits, const int64_t* labels, int B, int NC, int ld, float* row_loss,
-                 float* lse, hipStream_t s);
+                 float* lse, hipStream_t s, float smoothing = 0.f);
 // loss: [1 + B] floats (mean at [0], per-row terms after it; fixed-order sum)
 void ce_fwd(const bf16_raw* logits, const int64_t* labels, int B, int NC, int ld, float* loss,
-            float* lse, hipStream_t s);
+            float* lse, hipStream_t s, float smoothing = 0.f);
 void ce_bwd(const bf16_raw* logits, const int64_t* labels, const float* lse,
             const float* grad_out, int B, int NC, int ld, bf16_raw* dlogits, hipStream_t s,
-            float weight = 1.f);
+            float weight = 1.f, float smoothing = 0.f);
 void ce_fwd_weighted(const bf16_raw* logits, const int64_t* labels, int B, int NC, int ld,
                      float* out, float* acc, float weight, bool accumulate, float* rows,
-                     float* lse, hipStream_t s);
+                     float* lse, hipStream_t s, float smoothing = 0.f);
 // fp32 t[0:n) = 0 (n % 4 == 0, 16-B aligned); step[0] += 1
 void zero_f32(float* t, int64_t n, hipStream_t s);
 void add_f32(float* dst, const float* src, int64_t n, hipStream_t s);  // dst += src
@@ -391,6 +392,10 @@ void add_bf16(bf16_raw* a, const bf16_raw* b, int64_t n, hipStream_t s);
 void step_inc(float* step, hipStream_t s);
 void argmax_correct(const bf16_raw* logits, const int64_t* labels, int B, int NC, int ld,
                     int64_t* count, hipStream_t s);
+// count += #{rows whose label is among the k largest logits}; ties go to the lower index
+// (k = 1 is argmax_correct); out-of-range labels and NaN label logits are not counted
+void topk_correct(const bf16_raw* logits, const int64_t* labels, int B, int NC, int ld, int k,
+                  int64_t* count, hipStream_t s);
 
 // optim.hip (flat fp32 arenas)
 void adam_step(float* p, const float* g, float* m, float* v, bf16_raw* shadow,

@@ -11,6 +11,17 @@
 // Rows may be padded (row stride ld >= NC): classifier heads store their output dim
 // rounded up to a multiple of 32 so every GEMM of the head stays 16-B granular; the
 // backward writes zeros into the padding columns of dlogits.
+//
+// SMOOTH (label smoothing, torch's cross_entropy(label_smoothing=eps)): the row loss is
+// lse - (1-eps) * logit[label] - (eps/NC) * sum_c logit[c] and the gradient subtracts
+// (1-eps) * onehot + eps/NC instead of onehot.  The forward's only new quantity is the
+// per-row sum of the logits, accumulated in the same pass and reduced in the same fixed
+// order as (m, s); the backward needs only the two constants.  Everything smoothing adds
+// sits under "if constexpr (SMOOTH)", and eps == 0 launches the SMOOTH = false
+// instantiations: the plain loss runs the code it ran before smoothing existed.
+//
+// Top-k accuracy (topk_correct): no selection or sort - a row is correct iff fewer than k
+// columns outrank its label's logit, ties going to the lower index (argmax_kernel's rule).
 #include "common.h"
 #include "api.h"
 #include <cstdlib>
@@ -38,14 +49,52 @@ __device__ __forceinline__ void lse_merge(float& m, float& s, float m2, float s2
   m = mn;
 }
 
-template <int V>
+// Block-reduce the per-thread (m, s) - and, SMOOTH, the logit sum t - in a fixed order
+// (wave shuffle, then 4 LDS entries) and have thread 0 write the row's lse and loss term.
+template <bool SMOOTH>
+__device__ __forceinline__ void ce_row_finish(float m, float s, float t, const bf16_t* x, int row,
+                                              const int64_t* __restrict__ labels, int B, int NC,
+                                              float* __restrict__ row_loss,
+                                              float* __restrict__ lse_out, float eps) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float m2 = __shfl_xor(m, o, 64), s2 = __shfl_xor(s, o, 64);
+    lse_merge(m, s, m2, s2);
+    if constexpr (SMOOTH) t += __shfl_xor(t, o, 64);
+  }
+  __shared__ float sm[4], ss[4], st[SMOOTH ? 4 : 1];
+  const int w = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 0) {
+    sm[w] = m; ss[w] = s;
+    if constexpr (SMOOTH) st[w] = t;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    float M = sm[0], S = ss[0];
+    for (int i = 1; i < 4; ++i) lse_merge(M, S, sm[i], ss[i]);
+    const float lse = M + __logf(S);
+    lse_out[row] = lse;
+    const int64_t lab = labels[row];
+    if constexpr (SMOOTH) {
+      const float T = (st[0] + st[1]) + (st[2] + st[3]);
+      const float l = lse - (1.f - eps) * bf2f(x[lab >= 0 && lab < NC ? lab : 0]) -
+                      (eps / (float)NC) * T;
+      row_loss[row] = (lab >= 0 && lab < NC) ? l / (float)B : 0.f;
+    } else {
+      const float picked = (lab >= 0 && lab < NC) ? bf2f(x[lab]) : lse;
+      row_loss[row] = (lse - picked) / (float)B;
+    }
+  }
+}
+
+template <int V, bool SMOOTH = false>
 __global__ __launch_bounds__(256) void ce_fwd_kernel(const bf16_t* __restrict__ logits,
                                                       const int64_t* __restrict__ labels, int B,
                                                       int NC, int ld, float* __restrict__ row_loss,
-                                                      float* __restrict__ lse_out) {
+                                                      float* __restrict__ lse_out, float eps) {
   const int row = blockIdx.x;
   const bf16_t* x = logits + (size_t)row * ld;
-  float m = -INFINITY, s = 0.f;
+  float m = -INFINITY, s = 0.f, t = 0.f;
   const int nv = NC / V;
   for (int i = threadIdx.x; i < nv; i += 256) {
     float f[V];
@@ -59,41 +108,28 @@ __global__ __launch_bounds__(256) void ce_fwd_kernel(const bf16_t* __restrict__ 
     for (int j = 0; j < V; ++j) acc += __expf(f[j] - mn);
     m = mn;
     s = acc;
-  }
-  // wave reduce (m, s)
+    if constexpr (SMOOTH) {
 #pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float m2 = __shfl_xor(m, o, 64), s2 = __shfl_xor(s, o, 64);
-    lse_merge(m, s, m2, s2);
+      for (int j = 0; j < V; ++j) t += f[j];
+    }
   }
-  __shared__ float sm[4], ss[4];
-  const int w = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) { sm[w] = m; ss[w] = s; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    float M = sm[0], S = ss[0];
-    for (int i = 1; i < 4; ++i) lse_merge(M, S, sm[i], ss[i]);
-    const float lse = M + __logf(S);
-    lse_out[row] = lse;
-    const int64_t lab = labels[row];
-    const float picked = (lab >= 0 && lab < NC) ? bf2f(x[lab]) : lse;
-    row_loss[row] = (lse - picked) / (float)B;
-  }
+  ce_row_finish<SMOOTH>(m, s, t, x, row, labels, B, NC, row_loss, lse_out, eps);
 }
 
 // Padded rows (ld % 8 == 0, 16-B aligned; the 64,500-class head has ld = 64,512): 16-B
 // loads over the whole padded row with columns >= NC masked to -inf, U loads issued before
 // any is consumed.  The unpadded kernel above walked 64,500 columns in 8-B loads, one load
 // per online-LSE step, and streamed ~2.2 TB/s (30 us per 66 MB of logits).
-template <int U>
+template <int U, bool SMOOTH = false>
 __global__ __launch_bounds__(256) void ce_fwd_padded_kernel(const bf16_t* __restrict__ logits,
                                                              const int64_t* __restrict__ labels,
                                                              int B, int NC, int ld,
                                                              float* __restrict__ row_loss,
-                                                             float* __restrict__ lse_out) {
+                                                             float* __restrict__ lse_out,
+                                                             float eps) {
   const int row = blockIdx.x;
   const bf16_t* x = logits + (size_t)row * ld;
-  float m = -INFINITY, s = 0.f;
+  float m = -INFINITY, s = 0.f, t = 0.f;
   const int nv = ld / 8;
   for (int i0 = threadIdx.x; i0 < nv; i0 += 256 * U) {
     uint4 v[U];
@@ -112,6 +148,7 @@ __global__ __launch_bounds__(256) void ce_fwd_padded_kernel(const bf16_t* __rest
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
         if (c0 + j >= NC) f[j] = -INFINITY;
+        else if constexpr (SMOOTH) t += f[j];  // pad columns add 0, not the -inf mask
         lm = fmaxf(lm, f[j]);
       }
       const float mn = fmaxf(m, lm);
@@ -122,33 +159,17 @@ __global__ __launch_bounds__(256) void ce_fwd_padded_kernel(const bf16_t* __rest
       s = acc;
     }
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float m2 = __shfl_xor(m, o, 64), s2 = __shfl_xor(s, o, 64);
-    lse_merge(m, s, m2, s2);
-  }
-  __shared__ float sm[4], ss[4];
-  const int w = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) { sm[w] = m; ss[w] = s; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    float M = sm[0], S = ss[0];
-    for (int i = 1; i < 4; ++i) lse_merge(M, S, sm[i], ss[i]);
-    const float lse = M + __logf(S);
-    lse_out[row] = lse;
-    const int64_t lab = labels[row];
-    const float picked = (lab >= 0 && lab < NC) ? bf2f(x[lab]) : lse;
-    row_loss[row] = (lse - picked) / (float)B;
-  }
+  ce_row_finish<SMOOTH>(m, s, t, x, row, labels, B, NC, row_loss, lse_out, eps);
 }
 
-template <int V>
+// SMOOTH: onw = 1 - eps is the label's weight, unif = eps / NC every class's share.
+template <int V, bool SMOOTH = false>
 __global__ __launch_bounds__(256) void ce_bwd_kernel(const bf16_t* __restrict__ logits,
                                                       const int64_t* __restrict__ labels,
                                                       const float* __restrict__ lse,
                                                       const float* __restrict__ grad_out, int B,
                                                       int NC, int ld, bf16_t* __restrict__ dlogits,
-                                                      float weight) {
+                                                      float weight, float onw, float unif) {
   const float scale = grad_out[0] * weight / (float)B;
   const int nv = ld / V;  // whole padded row: columns >= NC get zero gradient
   const int64_t total = (int64_t)B * nv;
@@ -164,7 +185,12 @@ __global__ __launch_bounds__(256) void ce_bwd_kernel(const bf16_t* __restrict__ 
 #pragma unroll
     for (int j = 0; j < V; ++j) {
       float p = __expf(f[j] - l);
-      if (c0 + j == lab) p -= 1.f;
+      if constexpr (SMOOTH) {
+        p -= unif;
+        if (c0 + j == lab) p -= onw;
+      } else {
+        if (c0 + j == lab) p -= 1.f;
+      }
       f[j] = (c0 + j < NC) ? p * scale : 0.f;
     }
     if constexpr (V == 8) {
@@ -206,6 +232,63 @@ __global__ __launch_bounds__(256) void argmax_kernel(const bf16_t* __restrict__ 
   }
 }
 
+// Top-k accuracy: the row is correct iff fewer than k columns outrank its label, where
+// column c outranks the label when x[c] > x[label], or x[c] == x[label] and c < label
+// (argmax_kernel's tie rule, so k = 1 counts what argmax_correct counts).  Rows whose label
+// is outside [0, NC) or whose label logit is NaN are not counted (x[label] is not read for
+// the former); NaNs elsewhere compare false.  VEC: 16-B loads over the padded row
+// (ld % 8 == 0, 16-B aligned), U in flight as in ce_fwd_padded_kernel, columns >= NC
+// excluded.  Integer counts all the way, so the result does not depend on any order.
+template <bool VEC, int U>
+__global__ __launch_bounds__(256) void topk_kernel(const bf16_t* __restrict__ logits,
+                                                    const int64_t* __restrict__ labels, int NC,
+                                                    int ld, int k,
+                                                    unsigned long long* __restrict__ count) {
+  const int row = blockIdx.x;
+  const bf16_t* x = logits + (size_t)row * ld;
+  const int64_t lab64 = labels[row];
+  if (lab64 < 0 || lab64 >= NC) return;  // block-uniform
+  const int lab = (int)lab64;
+  const float xl = bf2f(x[lab]);
+  if (xl != xl) return;  // block-uniform
+  int n = 0;
+  if constexpr (VEC) {
+    const int nv = ld / 8;
+    for (int i0 = threadIdx.x; i0 < nv; i0 += 256 * U) {
+      uint4 v[U];
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const int i = i0 + u * 256;
+        v[u] = i < nv ? *(const uint4*)(x + (size_t)i * 8) : make_uint4(0u, 0u, 0u, 0u);
+      }
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const int c0 = (i0 + u * 256) * 8;
+        if (c0 >= NC) continue;
+        float f[8];
+        unpack8(v[u], f);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          const int c = c0 + j;
+          n += (c < NC && (f[j] > xl || (f[j] == xl && c < lab))) ? 1 : 0;
+        }
+      }
+    }
+  } else {
+    for (int c = threadIdx.x; c < NC; c += 256) {
+      const float v = bf2f(x[c]);
+      n += (v > xl || (v == xl && c < lab)) ? 1 : 0;
+    }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) n += __shfl_xor(n, o, 64);
+  __shared__ int sn[4];
+  const int w = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 0) sn[w] = n;
+  __syncthreads();
+  if (threadIdx.x == 0 && sn[0] + sn[1] + sn[2] + sn[3] < k) atomicAdd(count, 1ull);
+}
+
 // loss = sum of the per-row terms in a FIXED order (strided per-thread partial sums, then a
 // fixed tree): bitwise reproducible, unlike one float atomic per row (whose order varies
 // between launches), and one launch like the memset it replaces.
@@ -231,9 +314,9 @@ __global__ __launch_bounds__(256) void ce_loss_sum_kernel(const float* __restric
 
 // loss: [1 + B] floats - the mean loss at [0], the per-row terms after it
 void ce_fwd(const bf16_raw* logits, const int64_t* labels, int B, int NC, int ld, float* loss,
-            float* lse, hipStream_t s) {
+            float* lse, hipStream_t s, float smoothing) {
   float* rows = loss + 1;
-  ce_fwd_rows(logits, labels, B, NC, ld, rows, lse, s);
+  ce_fwd_rows(logits, labels, B, NC, ld, rows, lse, s, smoothing);
   hipLaunchKernelGGL(ce_loss_sum_kernel, dim3(1), dim3(256), 0, s, rows, B, loss,
                      0, 1.f, (float*)nullptr);
 }
@@ -242,52 +325,82 @@ void ce_fwd(const bf16_raw* logits, const int64_t* labels, int B, int NC, int ld
 // scratch.  Several heads (Inception's main + 0.4 * aux) sum into one loss this way.
 void ce_fwd_weighted(const bf16_raw* logits, const int64_t* labels, int B, int NC, int ld,
                      float* out, float* acc, float weight, bool accumulate, float* rows,
-                     float* lse, hipStream_t s) {
-  ce_fwd_rows(logits, labels, B, NC, ld, rows, lse, s);
+                     float* lse, hipStream_t s, float smoothing) {
+  ce_fwd_rows(logits, labels, B, NC, ld, rows, lse, s, smoothing);
   hipLaunchKernelGGL(ce_loss_sum_kernel, dim3(1), dim3(256), 0, s, rows, B, out,
                      accumulate ? 1 : 0, weight, acc);
 }
 
-void ce_fwd_rows(const bf16_raw* logits, const int64_t* labels, int B, int NC, int ld, float* loss,
-                 float* lse, hipStream_t s) {
+template <bool SMOOTH>
+static void ce_fwd_rows_t(const bf16_raw* logits, const int64_t* labels, int B, int NC, int ld,
+                          float* loss, float* lse, hipStream_t s, float eps) {
   if (ld % 8 == 0 && ld >= NC && reinterpret_cast<uintptr_t>(logits) % 16 == 0) {
-    hipLaunchKernelGGL(ce_fwd_padded_kernel<4>, dim3(B), dim3(256), 0, s, logits, labels, B, NC,
-                       ld, loss, lse);
+    hipLaunchKernelGGL((ce_fwd_padded_kernel<4, SMOOTH>), dim3(B), dim3(256), 0, s, logits,
+                       labels, B, NC, ld, loss, lse, eps);
     return;
   }
   const int g = NC % 8 == 0 && ld % 8 == 0 ? 8 : (NC % 4 == 0 && ld % 4 == 0 ? 4 : 1);
   if (g == 8)
-    hipLaunchKernelGGL(ce_fwd_kernel<8>, dim3(B), dim3(256), 0, s, logits, labels, B, NC, ld, loss,
-                       lse);
+    hipLaunchKernelGGL((ce_fwd_kernel<8, SMOOTH>), dim3(B), dim3(256), 0, s, logits, labels, B,
+                       NC, ld, loss, lse, eps);
   else if (g == 4)
-    hipLaunchKernelGGL(ce_fwd_kernel<4>, dim3(B), dim3(256), 0, s, logits, labels, B, NC, ld, loss,
-                       lse);
+    hipLaunchKernelGGL((ce_fwd_kernel<4, SMOOTH>), dim3(B), dim3(256), 0, s, logits, labels, B,
+                       NC, ld, loss, lse, eps);
   else
-    hipLaunchKernelGGL(ce_fwd_kernel<1>, dim3(B), dim3(256), 0, s, logits, labels, B, NC, ld, loss,
-                       lse);
+    hipLaunchKernelGGL((ce_fwd_kernel<1, SMOOTH>), dim3(B), dim3(256), 0, s, logits, labels, B,
+                       NC, ld, loss, lse, eps);
+}
+
+// smoothing == 0 launches the SMOOTH = false instantiations (the plain loss, unchanged)
+void ce_fwd_rows(const bf16_raw* logits, const int64_t* labels, int B, int NC, int ld, float* loss,
+                 float* lse, hipStream_t s, float smoothing) {
+  if (smoothing != 0.f) ce_fwd_rows_t<true>(logits, labels, B, NC, ld, loss, lse, s, smoothing);
+  else ce_fwd_rows_t<false>(logits, labels, B, NC, ld, loss, lse, s, 0.f);
+}
+
+template <bool SMOOTH>
+static void ce_bwd_t(const bf16_raw* logits, const int64_t* labels, const float* lse,
+                     const float* grad_out, int B, int NC, int ld, bf16_raw* dlogits,
+                     hipStream_t s, float weight, float eps) {
+  const int V = (ld % 8 == 0) ? 8 : (ld % 4 == 0 ? 4 : 1);
+  const int64_t total = (int64_t)B * (ld / V);
+  const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>((total + 255) / 256, 8192));
+  const float onw = 1.f - eps, unif = eps / (float)NC;
+  if (V == 8)
+    hipLaunchKernelGGL((ce_bwd_kernel<8, SMOOTH>), dim3(blocks), dim3(256), 0, s, logits, labels,
+                       lse, grad_out, B, NC, ld, dlogits, weight, onw, unif);
+  else if (V == 4)
+    hipLaunchKernelGGL((ce_bwd_kernel<4, SMOOTH>), dim3(blocks), dim3(256), 0, s, logits, labels,
+                       lse, grad_out, B, NC, ld, dlogits, weight, onw, unif);
+  else
+    hipLaunchKernelGGL((ce_bwd_kernel<1, SMOOTH>), dim3(blocks), dim3(256), 0, s, logits, labels,
+                       lse, grad_out, B, NC, ld, dlogits, weight, onw, unif);
 }
 
 void ce_bwd(const bf16_raw* logits, const int64_t* labels, const float* lse,
             const float* grad_out, int B, int NC, int ld, bf16_raw* dlogits, hipStream_t s,
-            float weight) {
-  const int V = (ld % 8 == 0) ? 8 : (ld % 4 == 0 ? 4 : 1);
-  const int64_t total = (int64_t)B * (ld / V);
-  const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>((total + 255) / 256, 8192));
-  if (V == 8)
-    hipLaunchKernelGGL(ce_bwd_kernel<8>, dim3(blocks), dim3(256), 0, s, logits, labels, lse,
-                       grad_out, B, NC, ld, dlogits, weight);
-  else if (V == 4)
-    hipLaunchKernelGGL(ce_bwd_kernel<4>, dim3(blocks), dim3(256), 0, s, logits, labels, lse,
-                       grad_out, B, NC, ld, dlogits, weight);
+            float weight, float smoothing) {
+  if (smoothing != 0.f)
+    ce_bwd_t<true>(logits, labels, lse, grad_out, B, NC, ld, dlogits, s, weight, smoothing);
   else
-    hipLaunchKernelGGL(ce_bwd_kernel<1>, dim3(blocks), dim3(256), 0, s, logits, labels, lse,
-                       grad_out, B, NC, ld, dlogits, weight);
+    ce_bwd_t<false>(logits, labels, lse, grad_out, B, NC, ld, dlogits, s, weight, 0.f);
 }
 
 void argmax_correct(const bf16_raw* logits, const int64_t* labels, int B, int NC, int ld,
                     int64_t* count, hipStream_t s) {
   hipLaunchKernelGGL(argmax_kernel, dim3(B), dim3(256), 0, s, logits, labels, NC, ld,
                      (unsigned long long*)count);
+}
+
+// count += #{rows whose label is among the k largest logits} (ties to the lower index)
+void topk_correct(const bf16_raw* logits, const int64_t* labels, int B, int NC, int ld, int k,
+                  int64_t* count, hipStream_t s) {
+  if (ld % 8 == 0 && ld >= NC && reinterpret_cast<uintptr_t>(logits) % 16 == 0)
+    hipLaunchKernelGGL((topk_kernel<true, 4>), dim3(B), dim3(256), 0, s, logits, labels, NC, ld,
+                       k, (unsigned long long*)count);
+  else
+    hipLaunchKernelGGL((topk_kernel<false, 1>), dim3(B), dim3(256), 0, s, logits, labels, NC, ld,
+                       k, (unsigned long long*)count);
 }
 
 }  // namespace mpa

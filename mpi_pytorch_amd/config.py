@@ -74,6 +74,7 @@ class Config:
     # (data/augment.py; off by default = the reference's ToTensor -> Resize -> Normalize)
     augment: str = "none"                  # none | flip | rrc (random-resized crop + flip)
     aug_scale_min: float = 0.08            # rrc: smallest crop, as a fraction of the image area
+    label_smoothing: float = 0.0           # training-loss label smoothing in [0, 1] (0 = off)
     bucket_mb: float = 16.0                # gradient all-reduce bucket size (MiB)
     grad_comm_dtype: str = "fp32"          # fp32 | bf16 (wire dtype of the gradient all-reduce)
     overlap_comm: bool = True              # launch bucket all-reduce during backward
@@ -91,6 +92,7 @@ class Config:
     eval_lanes: int = 1                    # predictor lanes in the eval pipeline
     eval_batch: int = 64
     eval_assign: str = "random"            # random (reference) | roundrobin
+    eval_topk: int = 0                     # also report top-k accuracy (0 or 1: top-1 only)
     eval_src: int = 0                      # synthetic eval source side (0: the model input size)
     max_steps: int = 0                     # stop an epoch early (0 = full epoch)
     checksum_every: int = 0                # cross-rank replica checksum period (steps, 0=off)
@@ -121,6 +123,10 @@ class Config:
             raise ValueError("augment must be none|flip|rrc")
         if not 0.0 < self.aug_scale_min <= 1.0:
             raise ValueError("aug_scale_min must be in (0, 1]")
+        if not 0.0 <= self.label_smoothing <= 1.0:
+            raise ValueError("label_smoothing must be in [0, 1]")
+        if self.eval_topk < 0:
+            raise ValueError("eval_topk must be >= 0 (0 or 1 = top-1 only)")
 
     # -----------------------------------------------------------------------------------
     @property

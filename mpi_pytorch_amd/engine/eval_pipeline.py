@@ -65,7 +65,8 @@ def load_predictor(cfg: Config, device, ckpt_path: Optional[str] = None):
 
 class StreamPipeline:
     def __init__(self, model, device, out_hw, lanes: int = 1, depth: int = 4,
-                 assign: str = "random", seed: int = 0, mode: int = 1, cpad=None, pad=None):
+                 assign: str = "random", seed: int = 0, mode: int = 1, cpad=None, pad=None,
+                 topk: int = 0):
         self.model = model
         if cpad is None:  # the model stem's input layout (models.input_spec)
             spec = input_spec(model, out_hw)
@@ -86,9 +87,23 @@ class StreamPipeline:
             self.lane_streams = [torch.cuda.Stream(self.device) for _ in range(self.lanes)]
         self.counts = [torch.zeros(1, dtype=torch.int64, device=self.device)
                        for _ in range(self.lanes)]
+        # topk > 1: a second per-lane counter of rows whose label is among the k largest
+        # logits, filled from the same forward as ``counts``
+        self.topk = int(topk) if topk and topk > 1 else 0
+        self.topk_counts = [torch.zeros(1, dtype=torch.int64, device=self.device)
+                            for _ in range(self.lanes)] if self.topk else []
         self.seen = [0] * self.lanes
         self._pinned = {}
         self._last_slot = None
+
+    def _count(self, out, labels, lane: int) -> None:
+        Fn.count_correct(out, labels, self.counts[lane])
+        if self.topk:
+            Fn.count_topk(out, labels, self.topk, self.topk_counts[lane])
+
+    def topk_correct(self) -> List[int]:
+        """Per-lane top-k correct counts (empty unless ``topk > 1``); call after a run."""
+        return [int(c.item()) for c in self.topk_counts]
 
     def _lane_for(self, i: int) -> int:
         if self.assign == "roundrobin":
@@ -155,7 +170,7 @@ class StreamPipeline:
                     x.record_stream(s)
                     y = labels.pin_memory().to(self.device, non_blocking=True)
                     out = self.model(x)
-                    Fn.count_correct(out, y, self.counts[lane])
+                    self._count(out, y, lane)
                     done = torch.cuda.Event()
                     done.record(s)
                 inflight.append(done)
@@ -163,7 +178,7 @@ class StreamPipeline:
                     inflight.pop(0).synchronize()
             else:
                 out = self.model(x)
-                Fn.count_correct(out, labels, self.counts[lane])
+                self._count(out, labels, lane)
             self.seen[lane] += int(labels.shape[0])
         if self.cuda:
             for s in self.lane_streams:
@@ -212,7 +227,7 @@ class StreamPipeline:
                 x.record_stream(s)
                 lab_d.record_stream(s)
                 out = self.model(x)
-                Fn.count_correct(out, lab_d, self.counts[lane])
+                self._count(out, lab_d, lane)
                 done = torch.cuda.Event()
                 done.record(s)
             inflight.append(done)
@@ -360,7 +375,7 @@ def run_pipeline(cfg: Config, ckpt_path: Optional[str] = None, max_images: int =
         source = SyntheticImages((side, side) if side > 0 else tuple(out_hw))
     model = load_predictor(cfg, world.device, ckpt_path)
     pipe = StreamPipeline(model, world.device, out_hw, cfg.eval_lanes, assign=cfg.eval_assign,
-                          seed=cfg.seed + world.rank)
+                          seed=cfg.seed + world.rank, topk=cfg.eval_topk)
     t0 = time.perf_counter()
     if world.device.type == "cuda":
         pitch = None
@@ -388,8 +403,13 @@ def run_pipeline(cfg: Config, ckpt_path: Optional[str] = None, max_images: int =
         acc_local += a
         log.info("Finished node {}, acc {}".format(world.rank * pipe.lanes + lane + 3, a))
     total = reduce_scalar(acc_local, root=0)
+    total_k = None
+    if pipe.topk:
+        total_k = reduce_scalar(sum(pipe.topk_correct()) / max(dataset_size, 1), root=0)
     if world.rank == 0:
         log.info("Accuracy is {}".format(total))
+        if pipe.topk:
+            log.info("Top-{} accuracy is {}".format(pipe.topk, total_k))
         # the source extent is part of the number: a synthetic source at the model's input
         # size skips the downscale real ~1000x677 herbarium JPEGs need (cfg.eval_src)
         src = "real images" if isinstance(source, FolderImages) else \

@@ -44,15 +44,17 @@ def build_model(name: str, num_classes: int, feature_extract: bool, device: torc
     return model, input_size
 
 
-def loss_fn(out, labels, acc=None):
+def loss_fn(out, labels, acc=None, label_smoothing=0.0):
     """CE; Inception's train-mode (logits, aux) uses loss + 0.4 * aux_loss (the documented
     fix of the reference's broken Inception path), one fused native op.
-    ``acc``: device scalar the loss is also added to (the trainer's running sum)."""
+    ``acc``: device scalar the loss is also added to (the trainer's running sum);
+    ``label_smoothing``: torch's ``label_smoothing``, applied to every head."""
     if isinstance(out, (tuple, InceptionOutputs)):
         logits, aux = out[0], out[1]
         heads = [(aux, 0.4)] if aux is not None else None
-        return Fn.cross_entropy(logits, labels, acc=acc, heads=heads)
-    return Fn.cross_entropy(out, labels, acc=acc)
+        return Fn.cross_entropy(logits, labels, acc=acc, heads=heads,
+                                label_smoothing=label_smoothing)
+    return Fn.cross_entropy(out, labels, acc=acc, label_smoothing=label_smoothing)
 
 
 # MPA_WGRAD_STREAM_DDP=1: side-stream weight gradients with several ranks too (the bucket
@@ -181,10 +183,11 @@ class StepTimer:
 
 
 class TrainStep:
-    def __init__(self, model: nn.Module, optimizer, world: World):
+    def __init__(self, model: nn.Module, optimizer, world: World, label_smoothing: float = 0.0):
         self.model = model
         self.opt = optimizer
         self.world = world
+        self.label_smoothing = float(label_smoothing)  # a host constant: graph-capture safe
         self.arena: ParamArena = model._mpa_arena
         self.bucketer: GradBucketer = model._mpa_bucketer
         self.opt.grad_scale = 1.0 / world.world_size
@@ -231,7 +234,7 @@ class TrainStep:
         Fn.branch_streams(single)
         try:
             out = self.model(x)
-            loss = loss_fn(out, y, acc=self.loss_sum)
+            loss = loss_fn(out, y, acc=self.loss_sum, label_smoothing=self.label_smoothing)
         except BaseException:
             Fn.branch_streams(False)
             raise
@@ -381,9 +384,11 @@ def build_training(name: str, num_classes: int, device, world: World, lr: float,
                    optimizer: str = "adam", momentum: float = 0.9, weight_decay: float = 0.0,
                    feature_extract: bool = False, bucket_mb: float = 16.0, overlap: bool = True,
                    comm_dtype: str = "fp32", comm_ctas: Optional[int] = None,
-                   schedule: Optional[dict] = None, clip_grad_norm: float = 0.0):
+                   schedule: Optional[dict] = None, clip_grad_norm: float = 0.0,
+                   label_smoothing: float = 0.0):
     """``schedule``: keyword arguments of ``optim.set_schedule`` (None: constant LR);
-    ``clip_grad_norm`` > 0: global-norm gradient clipping (``optim.set_clip``)."""
+    ``clip_grad_norm`` > 0: global-norm gradient clipping (``optim.set_clip``);
+    ``label_smoothing``: the training loss's label smoothing in [0, 1]."""
     model, input_size = build_model(name, num_classes, feature_extract, device, world,
                                     bucket_mb=bucket_mb, overlap=overlap, comm_dtype=comm_dtype,
                                     comm_ctas=comm_ctas)
@@ -394,4 +399,4 @@ def build_training(name: str, num_classes: int, device, world: World, lr: float,
         opt.set_clip(clip_grad_norm)
     sync_params(model)
     model.train()
-    return model, opt, TrainStep(model, opt, world), input_size
+    return model, opt, TrainStep(model, opt, world, label_smoothing), input_size

@@ -222,7 +222,8 @@ def run_training(cfg: Config) -> dict:
         cfg.MODEL_NAME, cfg.NUM_CLASSES, dev, world, cfg.LR, cfg.optimizer, cfg.momentum,
         cfg.weight_decay, cfg.FEATURE_EXTRACT, cfg.bucket_mb, cfg.overlap_comm,
         cfg.grad_comm_dtype, None if cfg.grad_comm_ctas < 0 else cfg.grad_comm_ctas,
-        schedule=schedule, clip_grad_norm=cfg.clip_grad_norm)
+        schedule=schedule, clip_grad_norm=cfg.clip_grad_norm,
+        label_smoothing=cfg.label_smoothing)
     log.info("_Model Created: {}".format(cfg.MODEL_NAME))
     spec = input_spec(model, out_hw)
     for ld in (train_loader, val_loader):
@@ -307,9 +308,13 @@ def run_training(cfg: Config) -> dict:
             log.info("_Checkpoint saved")
             if val_loader is not None:
                 log.info("_Evaluating model")
-                acc = evaluate(model, val_loader)
+                topk = cfg.eval_topk if cfg.eval_topk > 1 else 0
+                acc, acc_k = _evaluate(model, val_loader, topk)
                 rec["acc"] = acc
                 log.info("_Epoch: {} | Acc: {}".format(epoch, acc))
+                if topk:
+                    rec["acc_top{}".format(topk)] = acc_k
+                    log.info("_Epoch: {} | Top-{} Acc: {}".format(epoch, topk, acc_k))
         metrics.write(**rec)
         history.append(rec)
         if size > 1:
@@ -320,15 +325,25 @@ def run_training(cfg: Config) -> dict:
 
 
 @torch.no_grad()
-def evaluate(model, loader: ManifestBatches) -> float:
-    """Rank-0 accuracy over a loader (main.py:173-185)."""
+def _evaluate(model, loader: ManifestBatches, topk: int = 0):
+    """(top-1 accuracy, top-k accuracy or None) from one pass: each batch's forward feeds
+    both counters."""
     model.eval()
     dev = loader.device
     count = torch.zeros(1, dtype=torch.int64, device=dev)
+    count_k = torch.zeros(1, dtype=torch.int64, device=dev) if topk > 1 else None
     n = 0
     for x, y in loader.epoch(0):
         out = model(x)
         Fn.count_correct(out, y, count)
+        if count_k is not None:
+            Fn.count_topk(out, y, topk, count_k)
         n += x.shape[0]
     model.train()
-    return float(count.item()) / max(n, 1)
+    return (float(count.item()) / max(n, 1),
+            float(count_k.item()) / max(n, 1) if count_k is not None else None)
+
+
+def evaluate(model, loader: ManifestBatches) -> float:
+    """Rank-0 accuracy over a loader (main.py:173-185)."""
+    return _evaluate(model, loader)[0]

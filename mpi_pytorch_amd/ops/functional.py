@@ -1302,12 +1302,13 @@ class _CrossEntropy(torch.autograd.Function):
     by its weight - no elementwise ATen ops for Inception's ``loss + 0.4 * aux_loss``."""
 
     @staticmethod
-    def forward(ctx, labels, weights, acc, *logits):
+    def forward(ctx, labels, weights, acc, smoothing, *logits):
         k = K(logits[0])
         out = torch.empty(1, device=logits[0].device, dtype=torch.float32)
-        lses = [k.ce_fwd_weighted(lg, labels, out, _or_empty(acc, lg), float(w), i > 0)
+        lses = [k.ce_fwd_weighted(lg, labels, out, _or_empty(acc, lg), float(w), i > 0, smoothing)
                 for i, (lg, w) in enumerate(zip(logits, weights))]
         ctx.weights = weights
+        ctx.smoothing = smoothing  # one eps for every head, as a torch criterion applies it
         ctx.save_for_backward(labels, *logits, *lses)
         return out.reshape(())
 
@@ -1317,31 +1318,40 @@ class _CrossEntropy(torch.autograd.Function):
         labels, n = saved[0], len(ctx.weights)
         logits, lses = saved[1:1 + n], saved[1 + n:]
         go = go.reshape(1).float().contiguous()
-        gs = [K(lg).ce_bwd(lg, labels, lse, go, float(w))
+        gs = [K(lg).ce_bwd(lg, labels, lse, go, float(w), ctx.smoothing)
               for lg, lse, w in zip(logits, lses, ctx.weights)]
-        return (None, None, None) + tuple(gs)
+        return (None, None, None, None) + tuple(gs)
 
 
 def cross_entropy(logits, labels, weight: float = 1.0, acc: Optional[torch.Tensor] = None,
-                  heads=None):
+                  heads=None, label_smoothing: float = 0.0):
     """Mean softmax cross-entropy (``nn.CrossEntropyLoss()`` at main.py:134,150).
 
     ``heads``: extra (logits, weight) terms summed into the same loss (Inception aux);
-    ``acc``: a float32 device scalar the loss is also added to (no host sync)."""
+    ``acc``: a float32 device scalar the loss is also added to (no host sync);
+    ``label_smoothing``: torch's ``label_smoothing`` in [0, 1], applied to every head."""
+    eps = float(label_smoothing)
+    if not 0.0 <= eps <= 1.0:
+        raise ValueError("label_smoothing must be in [0, 1], got %r" % (label_smoothing,))
     lg = [logits] + [h[0] for h in (heads or [])]
     ws = (float(weight),) + tuple(float(h[1]) for h in (heads or []))
     if torch.is_grad_enabled() and any(t.requires_grad for t in lg):
-        return _CrossEntropy.apply(labels, ws, acc, *lg)
+        return _CrossEntropy.apply(labels, ws, acc, eps, *lg)
     k = K(logits)
     out = torch.empty(1, device=logits.device, dtype=torch.float32)
     for i, (t, w) in enumerate(zip(lg, ws)):
-        k.ce_fwd_weighted(t, labels, out, _or_empty(acc, t), w, i > 0)
+        k.ce_fwd_weighted(t, labels, out, _or_empty(acc, t), w, i > 0, eps)
     return out.reshape(())
 
 
 def count_correct(logits, labels, count: torch.Tensor) -> None:
     """count += #(argmax(logits) == labels)  (main.py:182-183)."""
     K(logits).argmax_correct(logits, labels, count)
+
+
+def count_topk(logits, labels, k: int, count: torch.Tensor) -> None:
+    """count += #(labels among the k largest logits), ties to the lower index."""
+    K(logits).topk_correct(logits, labels, int(k), count)
 
 
 def preprocess(img_u8, out_hw, mean, std, mode: int = 0, cpad: int = 3,

@@ -544,23 +544,29 @@ def linear_wgrad(dy, x, dw, overwrite=False):
 
 
 # --------------------------------------------------------------------------- loss / acc
-def ce_fwd(logits, labels):
+def ce_fwd(logits, labels, smoothing=0.0):
+    """``smoothing``: torch's ``label_smoothing`` - the target is (1 - eps) * onehot + eps / NC."""
     lf = _f(logits)
     lse = torch.logsumexp(lf, dim=1)
     picked = lf.gather(1, labels.view(-1, 1).long()).squeeze(1)
-    loss = (lse - picked).mean().reshape(1)
-    return loss, lse
+    if smoothing:
+        rows = lse - (1.0 - smoothing) * picked - (smoothing / lf.shape[1]) * lf.sum(1)
+    else:
+        rows = lse - picked
+    return rows.mean().reshape(1), lse
 
 
-def ce_bwd(logits, labels, lse, grad_out, weight=1.0):
-    B = logits.shape[0]
+def ce_bwd(logits, labels, lse, grad_out, weight=1.0, smoothing=0.0):
+    B, NC = logits.shape
     p = torch.exp(_f(logits) - lse[:, None])
-    p[torch.arange(B, device=logits.device), labels.long()] -= 1.0
+    if smoothing:
+        p -= smoothing / NC
+    p[torch.arange(B, device=logits.device), labels.long()] -= 1.0 - smoothing
     return (p * (_f(grad_out).reshape(()) * weight / B)).to(logits.dtype)
 
 
-def ce_fwd_weighted(logits, labels, out, acc, weight, accumulate):
-    loss, lse = ce_fwd(logits, labels)
+def ce_fwd_weighted(logits, labels, out, acc, weight, accumulate, smoothing=0.0):
+    loss, lse = ce_fwd(logits, labels, smoothing)
     v = loss.reshape(1) * weight
     if accumulate:
         out[:1] += v
@@ -582,6 +588,25 @@ def step_inc(step):
 def argmax_correct(logits, labels, count):
     pred = _f(logits).argmax(1)
     count.add_((pred == labels.long()).sum().to(count.dtype))
+
+
+def topk_correct(logits, labels, k, count):
+    """count += #{rows whose label is among the k largest logits}.  No sort: the label's
+    rank is the number of columns that beat it, a tie going to the lower index (argmax's
+    rule, so k = 1 is ``argmax_correct``).  Rows whose label is outside [0, NC) or whose
+    label logit is NaN are not counted; NaNs elsewhere compare false."""
+    if k < 1:
+        raise ValueError("topk_correct: k must be >= 1, got %r" % (k,))
+    lf = _f(logits)
+    NC = lf.shape[1]
+    lab = labels.long()
+    valid = (lab >= 0) & (lab < NC)
+    safe = lab.clamp(0, NC - 1).view(-1, 1)
+    xl = lf.gather(1, safe)
+    idx = torch.arange(NC, device=lf.device).view(1, -1)
+    rank = ((lf > xl) | ((lf == xl) & (idx < safe))).sum(1)
+    ok = valid & ~torch.isnan(xl.squeeze(1)) & (rank < k)
+    count.add_(ok.sum().to(count.dtype))
 
 
 # ----------------------------------------------------------------------------- optimizer

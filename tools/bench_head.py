@@ -1,8 +1,11 @@
 """Timing of the classifier-head ops of the headline step (ResNet-18 @64,500 classes):
 linear fwd / dgrad / wgrad at [batch, 512] x [64,512, 512], the fused CE fwd / bwd, and a
-wgrad tile sweep (forced BM x BN, splits).
+wgrad tile sweep (forced BM x BN, splits).  The loss head is also timed smoothed
+(label smoothing 0.1) against plain, and topk_correct (k = 1, 5) against argmax_correct: each
+variant warmed, three alternating repetitions, so the plain kernel's own spread stands next
+to every difference.
 
-    python tools/bench_head.py [batch] [iters]
+    python tools/bench_head.py [batch] [iters] [loss]     (loss: stop after the loss head)
 """
 import os
 import sys
@@ -53,6 +56,30 @@ loss, lse = C.ce_fwd(logits, labels)
 go = torch.ones(1, device=dev)
 print("%-14s %8.1f us" % ("ce_fwd", timeit(lambda: C.ce_fwd(logits, labels))))
 print("%-14s %8.1f us" % ("ce_bwd", timeit(lambda: C.ce_bwd(logits, labels, lse, go))))
+
+_, lse_s = C.ce_fwd(logits, labels, 0.1)
+cnt = torch.zeros(1, dtype=torch.int64, device=dev)
+groups = [
+    [("ce_fwd", lambda: C.ce_fwd(logits, labels)),
+     ("ce_fwd eps=.1", lambda: C.ce_fwd(logits, labels, 0.1))],
+    [("ce_bwd", lambda: C.ce_bwd(logits, labels, lse, go)),
+     ("ce_bwd eps=.1", lambda: C.ce_bwd(logits, labels, lse_s, go, 1.0, 0.1))],
+    [("argmax_correct", lambda: C.argmax_correct(logits, labels, cnt)),
+     ("topk k=1", lambda: C.topk_correct(logits, labels, 1, cnt)),
+     ("topk k=5", lambda: C.topk_correct(logits, labels, 5, cnt))],
+]
+print("loss head, 3 alternating repetitions: us (min .. max)")
+for group in groups:
+    times = {name: [] for name, _ in group}
+    for _ in range(3):
+        for name, fn in group:
+            times[name].append(timeit(fn))
+    for name, _ in group:
+        t = times[name]
+        print("%-14s %s  (%.1f .. %.1f)" % (name, " ".join("%8.1f" % v for v in t),
+                                            min(t), max(t)))
+if len(sys.argv) > 3 and sys.argv[3] == "loss":
+    sys.exit(0)
 
 print("wgrad sweep (BM x BN / splits): us")
 for bm, bn in ((128, 256), (256, 256), (128, 128), (64, 128), (64, 256)):
