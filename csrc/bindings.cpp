@@ -1440,6 +1440,125 @@ void sgd_step_dev(Tensor p, Tensor g, Tensor buf, Tensor shadow, Tensor step, Te
                     nesterov ? 1 : 0, cur_stream());
 }
 
+// ---- layer-wise optimizers on the segment plan (AdamW / LAMB / LARS)
+static void check_plan(const Tensor& seg, const Tensor& chunk_seg, const Tensor& like) {
+  CHECK_CUDA(like);
+  TORCH_CHECK(seg.scalar_type() == torch::kInt64 && seg.dim() == 2 &&
+                  seg.size(1) == mpa::SEG_COLS && seg.is_contiguous() &&
+                  seg.device() == like.device(), "plan: seg [nseg][5] int64 on the arena's device");
+  TORCH_CHECK(chunk_seg.scalar_type() == torch::kInt32 && chunk_seg.dim() == 1 &&
+                  chunk_seg.is_contiguous() && chunk_seg.device() == like.device() &&
+                  chunk_seg.numel() < INT32_MAX && seg.size(0) < INT32_MAX,
+              "plan: chunk_seg [nchunks] int32 on the arena's device");
+}
+
+static void check_arena(const Tensor& t, const Tensor& like, const char* what) {
+  TORCH_CHECK(t.scalar_type() == torch::kFloat32 && t.is_contiguous() &&
+                  t.device() == like.device() && t.numel() >= like.numel() &&
+                  reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0,
+              what, ": contiguous 16-B aligned fp32 of at least the arena's length");
+}
+
+static void check_f32_n(const Tensor& t, int64_t n, const Tensor& like, const char* what) {
+  TORCH_CHECK(t.scalar_type() == torch::kFloat32 && t.is_contiguous() &&
+                  t.device() == like.device() && t.numel() >= n, what, ": fp32 of at least ", n,
+              " elements on the arena's device");
+}
+
+static mpa::bf16_raw* check_shadow(const Tensor& shadow, const Tensor& p) {
+  if (!has(shadow)) return nullptr;
+  TORCH_CHECK(shadow.scalar_type() == torch::kBFloat16 && shadow.is_contiguous() &&
+                  shadow.device() == p.device() && shadow.numel() >= p.numel() &&
+                  reinterpret_cast<uintptr_t>(shadow.data_ptr()) % 8 == 0, "shadow: bf16 arena");
+  return bpm(shadow);
+}
+
+void seg_sqnorm(Tensor x, Tensor seg, Tensor chunk_seg, Tensor hyper, bool scaled, Tensor part) {
+  check_arena(x, x, "seg_sqnorm");
+  check_plan(seg, chunk_seg, x);
+  check_hyper(hyper, x);
+  check_f32_n(part, chunk_seg.numel(), x, "seg_sqnorm: part");
+  const c10::OptionalDeviceGuard gd(device_of(x));
+  mpa::seg_sqnorm(x.data_ptr<float>(), x.numel(), seg.data_ptr<int64_t>(),
+                  chunk_seg.data_ptr<int>(), (int)seg.size(0), (int)chunk_seg.numel(),
+                  hyper.data_ptr<float>(), scaled ? 1 : 0, part.data_ptr<float>(), cur_stream());
+}
+
+void lamb_norms(Tensor p, Tensor g, Tensor m, Tensor v, Tensor step, Tensor hyper, Tensor seg,
+                Tensor chunk_seg, Tensor part_p, Tensor part_u, double b1, double b2, double eps,
+                double wd) {
+  check_arena(p, p, "lamb_norms: p");
+  check_arena(g, p, "lamb_norms: g");
+  check_arena(m, p, "lamb_norms: m");
+  check_arena(v, p, "lamb_norms: v");
+  check_plan(seg, chunk_seg, p);
+  check_hyper(hyper, p);
+  check_f32_n(step, 1, p, "lamb_norms: step");
+  check_f32_n(part_p, chunk_seg.numel(), p, "lamb_norms: part_p");
+  check_f32_n(part_u, chunk_seg.numel(), p, "lamb_norms: part_u");
+  const c10::OptionalDeviceGuard gd(device_of(p));
+  mpa::lamb_norms(p.data_ptr<float>(), g.data_ptr<float>(), m.data_ptr<float>(),
+                  v.data_ptr<float>(), p.numel(), step.data_ptr<float>(),
+                  hyper.data_ptr<float>(), seg.data_ptr<int64_t>(), chunk_seg.data_ptr<int>(),
+                  (int)seg.size(0), (int)chunk_seg.numel(), part_p.data_ptr<float>(),
+                  part_u.data_ptr<float>(), b1, b2, eps, wd, cur_stream());
+}
+
+void trust_ratio(Tensor seg, Tensor chunk_seg, Tensor part_p, Tensor part_b, Tensor hyper,
+                 int64_t mode, double trust_coef, double wd, Tensor ratio, Tensor norms) {
+  check_plan(seg, chunk_seg, part_p);
+  check_hyper(hyper, part_p);
+  TORCH_CHECK(mode == mpa::TRUST_LAMB || mode == mpa::TRUST_LARS, "trust_ratio: mode");
+  check_f32_n(part_p, chunk_seg.numel(), part_p, "trust_ratio: part_p");
+  check_f32_n(part_b, chunk_seg.numel(), part_p, "trust_ratio: part_b");
+  check_f32_n(ratio, seg.size(0), part_p, "trust_ratio: ratio");
+  check_f32_n(norms, 2 * seg.size(0), part_p, "trust_ratio: norms");
+  const c10::OptionalDeviceGuard gd(device_of(part_p));
+  mpa::trust_ratio(seg.data_ptr<int64_t>(), (int)seg.size(0), (int)chunk_seg.numel(),
+                   part_p.data_ptr<float>(), part_b.data_ptr<float>(), hyper.data_ptr<float>(),
+                   (int)mode, trust_coef, wd, ratio.data_ptr<float>(), norms.data_ptr<float>(),
+                   cur_stream());
+}
+
+void lamb_step_dev(Tensor p, Tensor g, Tensor m, Tensor v, Tensor shadow, Tensor step,
+                   Tensor hyper, Tensor seg, Tensor chunk_seg, Tensor ratio, double b1, double b2,
+                   double eps, double wd, bool adamw) {
+  check_arena(p, p, "lamb_step_dev: p");
+  check_arena(g, p, "lamb_step_dev: g");
+  check_arena(m, p, "lamb_step_dev: m");
+  check_arena(v, p, "lamb_step_dev: v");
+  check_plan(seg, chunk_seg, p);
+  check_hyper(hyper, p);
+  check_f32_n(step, 1, p, "lamb_step_dev: step");
+  check_f32_n(ratio, seg.size(0), p, "lamb_step_dev: ratio");
+  mpa::bf16_raw* sh = check_shadow(shadow, p);
+  const c10::OptionalDeviceGuard gd(device_of(p));
+  mpa::lamb_step_dev(p.data_ptr<float>(), g.data_ptr<float>(), m.data_ptr<float>(),
+                     v.data_ptr<float>(), sh, p.numel(), step.data_ptr<float>(),
+                     hyper.data_ptr<float>(), seg.data_ptr<int64_t>(), chunk_seg.data_ptr<int>(),
+                     (int)seg.size(0), (int)chunk_seg.numel(), ratio.data_ptr<float>(), b1, b2,
+                     eps, wd, adamw ? 1 : 0, cur_stream());
+}
+
+void lars_step_dev(Tensor p, Tensor g, Tensor buf, Tensor shadow, Tensor step, Tensor hyper,
+                   Tensor seg, Tensor chunk_seg, Tensor ratio, double momentum, double dampening,
+                   double wd, bool nesterov) {
+  check_arena(p, p, "lars_step_dev: p");
+  check_arena(g, p, "lars_step_dev: g");
+  check_arena(buf, p, "lars_step_dev: buf");
+  check_plan(seg, chunk_seg, p);
+  check_hyper(hyper, p);
+  check_f32_n(step, 1, p, "lars_step_dev: step");
+  check_f32_n(ratio, seg.size(0), p, "lars_step_dev: ratio");
+  mpa::bf16_raw* sh = check_shadow(shadow, p);
+  const c10::OptionalDeviceGuard gd(device_of(p));
+  mpa::lars_step_dev(p.data_ptr<float>(), g.data_ptr<float>(), buf.data_ptr<float>(), sh,
+                     p.numel(), step.data_ptr<float>(), hyper.data_ptr<float>(),
+                     seg.data_ptr<int64_t>(), chunk_seg.data_ptr<int>(), (int)seg.size(0),
+                     (int)chunk_seg.numel(), ratio.data_ptr<float>(), momentum, dampening, wd,
+                     nesterov ? 1 : 0, cur_stream());
+}
+
 void transpose_krsc(Tensor w, Tensor wt, Tensor seg, int64_t total_tiles,
                     c10::optional<Tensor> step_inc) {
   CHECK_CUDA(w);
@@ -1897,6 +2016,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("hyper_update", &hyper_update);
   m.def("adam_step_dev", &adam_step_dev);
   m.def("sgd_step_dev", &sgd_step_dev);
+  m.def("seg_chunk", []() { return (int64_t)mpa::seg_chunk(); },
+        "largest chunk of the layer-wise optimizers' segment plan, in elements");
+  m.def("seg_sqnorm", &seg_sqnorm, "per-chunk sum of squares over the segment plan");
+  m.def("lamb_norms", &lamb_norms, "LAMB stage 1: per-chunk sum p^2 and sum u^2");
+  m.def("trust_ratio", &trust_ratio, "per-segment norms and trust ratio from the partials");
+  m.def("lamb_step_dev", &lamb_step_dev, "LAMB stage 2 / AdamW on the segment plan");
+  m.def("lars_step_dev", &lars_step_dev, "LARS on the segment plan");
   m.def("transpose_krsc", &transpose_krsc, py::arg("w"), py::arg("wt"), py::arg("seg"),
         py::arg("total_tiles"), py::arg("step_inc") = py::none());
   m.def("zero_f32", &zero_f32, "t.zero_() on the native path");

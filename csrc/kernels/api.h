@@ -438,6 +438,42 @@ void adam_step_dev(float* p, const float* g, float* m, float* v, bf16_raw* shado
 void sgd_step_dev(float* p, const float* g, float* buf, bf16_raw* shadow, const float* step,
                   const float* hyper, int64_t n, float momentum, float dampening, float wd,
                   int nesterov, hipStream_t s);
+// Layer-wise optimizers (AdamW / LAMB / LARS) on a segment plan over the arena.
+// seg [nseg][SEG_COLS] int64: parameter s's aligned slice, its chunks and its flags;
+// chunk_seg [nchunks] int32: the segment of each chunk (a segment's chunks are consecutive,
+// each at most seg_chunk() elements).  n: elements of the arena-shaped buffers; a plan
+// entry outside [0, n) is not followed.  All read lr / gradient scale / skip flag from
+// hyper and write nothing when hyper[HYPER_SKIP] != 0; no float atomics.
+enum { SEG_OFF = 0, SEG_LEN = 1, SEG_FIRST = 2, SEG_NCHUNK = 3, SEG_FLAGS = 4, SEG_COLS = 5 };
+enum { SEG_DECAY = 1, SEG_ADAPT = 2 };     // flag bits
+enum { TRUST_LAMB = 0, TRUST_LARS = 1 };  // trust_ratio modes
+int seg_chunk();
+// part[c] = sum over chunk c of (x * (scaled ? hyper[HYPER_SCALE] : 1))^2
+void seg_sqnorm(const float* x, int64_t n, const int64_t* seg, const int* chunk_seg, int nseg,
+                int nchunks, const float* hyper, int scaled, float* part, hipStream_t s);
+// LAMB stage 1: per chunk sum p^2 and sum u^2, u = m^ / (sqrt(v^) + eps) + wd_s * p from the
+// moments the step would produce; p, g, m, v are only read
+void lamb_norms(const float* p, const float* g, const float* m, const float* v, int64_t n,
+                const float* step, const float* hyper, const int64_t* seg, const int* chunk_seg,
+                int nseg, int nchunks, float* part_p, float* part_u, float b1, float b2,
+                float eps, float wd, hipStream_t s);
+// per segment: fixed-order sums of its partials -> norms[s] = (|p|, |b|) and ratio[s]
+// (TRUST_LAMB: |p| / |b|; TRUST_LARS: trust_coef * |p| / (|b| + wd_s * |p| + 1e-8); 1 when
+// the segment is not SEG_ADAPT or a norm is 0)
+void trust_ratio(const int64_t* seg, int nseg, int nchunks, const float* part_p,
+                 const float* part_b, const float* hyper, int mode, float trust_coef, float wd,
+                 float* ratio, float* norms, hipStream_t s);
+// LAMB stage 2: p -= lr * ratio[s] * u; adamw != 0: torch.optim.AdamW (p *= 1 - lr * wd_s,
+// then the Adam step; ratio is not read).  wd_s = wd on SEG_DECAY segments, else 0.
+void lamb_step_dev(float* p, const float* g, float* m, float* v, bf16_raw* shadow, int64_t n,
+                   const float* step, const float* hyper, const int64_t* seg,
+                   const int* chunk_seg, int nseg, int nchunks, const float* ratio, float b1,
+                   float b2, float eps, float wd, int adamw, hipStream_t s);
+// LARS: g' = ratio[s] * (g^ + wd_s * p), then sgd_step's momentum rule with wd = 0
+void lars_step_dev(float* p, const float* g, float* buf, bf16_raw* shadow, int64_t n,
+                   const float* step, const float* hyper, const int64_t* seg,
+                   const int* chunk_seg, int nseg, int nchunks, const float* ratio,
+                   float momentum, float dampening, float wd, int nesterov, hipStream_t s);
 // wt[c][t][k] = w[k][t][c] per segment (src_off, dst_off, K, RS, C, first_tile) of seg
 // step_inc (optional): the optimizer's step counter, incremented by the same launch
 void transpose_krsc(const bf16_raw* w, bf16_raw* wt, const int64_t* seg, int nseg,

@@ -290,6 +290,368 @@ void hyper_update(const float* step, const float* part, int nparts, float* hyper
   hipLaunchKernelGGL(hyper_kernel, dim3(1), dim3(256), 0, s, step, part, nparts, hyper, cfg);
 }
 
+// ------------------------------------------- layer-wise optimizers: AdamW / LAMB / LARS
+// The segment plan tells the flat-arena kernels which parameter an element belongs to.
+// seg: [nseg][SEG_COLS] int64 = (offset, aligned length, first chunk, chunk count, flags);
+// segment s is parameter s's aligned arena slice, the segments tile [0, n) and start on
+// 64-element boundaries, so a float4 never straddles two parameters.  Each segment is cut
+// into chunks of at most SEG_CHUNK elements, consecutive in the chunk table; chunk_seg[c]
+// is chunk c's segment.  One block per chunk: everything a block reads from the plan is
+// uniform, and a chunk never crosses a segment.
+// Norms: one float per chunk (wave64 shuffle -> LDS, fixed order), then trust_ratio_kernel
+// sums a segment's partials with one block in a fixed order.  No float atomics: a
+// parameter's norm depends only on (values, plan), so it is bitwise reproducible in every
+// mode and equal on every data-parallel rank.
+// Every kernel here takes lr / gradient scale / skip flag from the hyper record and writes
+// nothing when hyper[HYPER_SKIP] != 0.
+constexpr int SEG_CHUNK = 16384;  // elements: 256 threads x 8 float4 x 2 rounds
+
+struct Chunk {
+  int64_t off;  // first element
+  int n4;       // float4s (0: a malformed plan entry - touch nothing)
+  int seg;
+  int flags;
+};
+
+__device__ __forceinline__ Chunk chunk_of(const int64_t* __restrict__ seg,
+                                          const int* __restrict__ chunk_seg, int nseg, int c,
+                                          int64_t n) {
+  Chunk k;
+  k.seg = chunk_seg[c];
+  k.off = 0;
+  k.n4 = 0;
+  k.flags = 0;
+  if (k.seg < 0 || k.seg >= nseg) {
+    k.seg = 0;
+    return k;
+  }
+  const int64_t* d = seg + (int64_t)k.seg * SEG_COLS;
+  const int64_t rel = ((int64_t)c - d[SEG_FIRST]) * SEG_CHUNK;
+  const int64_t left = d[SEG_LEN] - rel;
+  const int64_t len = left < SEG_CHUNK ? left : (int64_t)SEG_CHUNK;
+  k.off = d[SEG_OFF] + rel;
+  k.flags = (int)d[SEG_FLAGS];
+  // the plan is built on the host (optim.py); an entry outside the arena is not followed
+  if (rel >= 0 && len > 0 && k.off >= 0 && (k.off & 3) == 0 && k.off + len <= n)
+    k.n4 = (int)(len / 4);
+  return k;
+}
+
+// block sums of two values; valid in thread 0
+__device__ __forceinline__ void block_sum2(float& a, float& b) {
+  __shared__ float ws[8];
+  a = wave_sum(a);
+  b = wave_sum(b);
+  if ((threadIdx.x & 63) == 0) {
+    ws[threadIdx.x >> 6] = a;
+    ws[4 + (threadIdx.x >> 6)] = b;
+  }
+  __syncthreads();
+  a = (ws[0] + ws[1]) + (ws[2] + ws[3]);
+  b = (ws[4] + ws[5]) + (ws[6] + ws[7]);
+}
+
+// part[c] = sum over chunk c of (x * scale)^2, scale = hyper[HYPER_SCALE] when scaled
+__global__ __launch_bounds__(256) void seg_sqnorm_kernel(const float* __restrict__ x, int64_t n,
+                                                         const int64_t* __restrict__ seg,
+                                                         const int* __restrict__ chunk_seg,
+                                                         int nseg,
+                                                         const float* __restrict__ hyper,
+                                                         int scaled, float* __restrict__ part) {
+  if (hyper[HYPER_SKIP] != 0.f) return;
+  const Chunk k = chunk_of(seg, chunk_seg, nseg, blockIdx.x, n);
+  const float sc = scaled ? hyper[HYPER_SCALE] : 1.f;
+  const float4* __restrict__ x4 = (const float4*)(x + k.off);
+  float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
+  for (int base = 0; base < k.n4; base += 256 * SQ_LOADS) {
+    float4 v[SQ_LOADS];
+#pragma unroll
+    for (int u = 0; u < SQ_LOADS; ++u) {
+      const int i = base + u * 256 + threadIdx.x;
+      v[u] = i < k.n4 ? x4[i] : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+#pragma unroll
+    for (int u = 0; u < SQ_LOADS; ++u) {
+      const float e0 = v[u].x * sc, e1 = v[u].y * sc, e2 = v[u].z * sc, e3 = v[u].w * sc;
+      a0 += e0 * e0;
+      a1 += e1 * e1;
+      a2 += e2 * e2;
+      a3 += e3 * e3;
+    }
+  }
+  float a = (a0 + a1) + (a2 + a3), b = 0.f;
+  block_sum2(a, b);
+  if (threadIdx.x == 0) part[blockIdx.x] = a;
+}
+
+// The element math of LAMB, shared by stage 1 (norms of the would-be update) and stage 2
+// (the update), so the u that is normed is bitwise the u that is applied: new moments
+// (adam_body's expressions with wd = 0) and u = m^ / (sqrt(v^) + eps) + wd_s * p.
+struct AdamCoef {
+  float b1, b2, eps, bc1, bc2s;
+};
+
+__device__ __forceinline__ AdamCoef adam_coef(const float* __restrict__ step, float b1, float b2,
+                                              float eps) {
+  const float t = step[0] + 1.f;
+  AdamCoef c;
+  c.b1 = b1;
+  c.b2 = b2;
+  c.eps = eps;
+  // once per thread, in double: 1 - powf(b2, t) loses b2^t / (1 - b2^t) = 125 ulps at t = 8,
+  // which the norm of u would carry as a relative error of 1e-5
+  c.bc1 = (float)(1.0 - pow((double)b1, (double)t));
+  c.bc2s = (float)sqrt(1.0 - pow((double)b2, (double)t));
+  return c;
+}
+
+__device__ __forceinline__ void moments_elem(float g, float gs, float& m, float& v,
+                                             const AdamCoef& c) {
+  // the contractions the compiler picks for adam_body's `b1 * m + (1 - b1) * gr` and
+  // `b2 * v + (1 - b2) * gr * gr`, spelled out: under -ffp-contract=fast the same source
+  // text fused the other product here, and the moments must be bitwise Adam's
+  // (test_updates_match_oracle compares them with adam_step_dev's)
+  const float gr = g * gs;
+  m = fmaf(1.f - c.b1, gr, c.b1 * m);
+  v = fmaf(gr, (1.f - c.b2) * gr, c.b2 * v);
+}
+
+__device__ __forceinline__ float lamb_elem(float p, float g, float gs, float& m, float& v,
+                                           float wd_s, const AdamCoef& c) {
+  moments_elem(g, gs, m, v, c);
+  const float denom = sqrtf(v) / c.bc2s + c.eps;
+  return (m / c.bc1) / denom + wd_s * p;
+}
+
+constexpr int LN_LOADS = 2;  // float4s per stream in flight per thread (4 streams)
+
+// LAMB stage 1: per chunk, sum p^2 and sum u^2 of the update direction the step would
+// apply.  Reads p, g, m, v; writes only the two partials.
+__global__ __launch_bounds__(256) void lamb_norms_kernel(
+    const float* __restrict__ p, const float* __restrict__ g, const float* __restrict__ m,
+    const float* __restrict__ v, int64_t n, const float* __restrict__ step,
+    const float* __restrict__ hyper, const int64_t* __restrict__ seg,
+    const int* __restrict__ chunk_seg, int nseg, float* __restrict__ part_p,
+    float* __restrict__ part_u, float b1, float b2, float eps, float wd) {
+  if (hyper[HYPER_SKIP] != 0.f) return;
+  const Chunk k = chunk_of(seg, chunk_seg, nseg, blockIdx.x, n);
+  const AdamCoef c = adam_coef(step, b1, b2, eps);
+  const float gs = hyper[HYPER_SCALE];
+  const float wd_s = (k.flags & SEG_DECAY) ? wd : 0.f;
+  const float4* __restrict__ p4 = (const float4*)(p + k.off);
+  const float4* __restrict__ g4 = (const float4*)(g + k.off);
+  const float4* __restrict__ m4 = (const float4*)(m + k.off);
+  const float4* __restrict__ v4 = (const float4*)(v + k.off);
+  float sp[4] = {0.f, 0.f, 0.f, 0.f}, su[4] = {0.f, 0.f, 0.f, 0.f};
+  const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+  for (int base = 0; base < k.n4; base += 256 * LN_LOADS) {
+    float4 pp[LN_LOADS], gg[LN_LOADS], mm[LN_LOADS], vv[LN_LOADS];
+#pragma unroll
+    for (int u = 0; u < LN_LOADS; ++u) {
+      const int i = base + u * 256 + threadIdx.x;
+      const bool in = i < k.n4;  // past the chunk: p = g = m = v = 0 gives u = 0
+      pp[u] = in ? p4[i] : z;
+      gg[u] = in ? g4[i] : z;
+      mm[u] = in ? m4[i] : z;
+      vv[u] = in ? v4[i] : z;
+    }
+#pragma unroll
+    for (int u = 0; u < LN_LOADS; ++u) {
+      const float* pf = (const float*)&pp[u];
+      const float* gf = (const float*)&gg[u];
+      float* mf = (float*)&mm[u];
+      float* vf = (float*)&vv[u];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const float uu = lamb_elem(pf[j], gf[j], gs, mf[j], vf[j], wd_s, c);
+        sp[j] += pf[j] * pf[j];
+        su[j] += uu * uu;
+      }
+    }
+  }
+  float a = (sp[0] + sp[1]) + (sp[2] + sp[3]), b = (su[0] + su[1]) + (su[2] + su[3]);
+  block_sum2(a, b);
+  if (threadIdx.x == 0) {
+    part_p[blockIdx.x] = a;
+    part_u[blockIdx.x] = b;
+  }
+}
+
+// One block per segment: fixed-order sums of its chunks' partials, the two norms and the
+// trust ratio.  LAMB: |p| / |u|.  LARS: trust_coef * |p| / (|g^| + wd_s * |p| + 1e-8), g^ the
+// scaled gradient.  1 when the segment is not adaptive or either norm is 0.
+__global__ __launch_bounds__(256) void trust_ratio_kernel(
+    const int64_t* __restrict__ seg, int nchunks, const float* __restrict__ part_p,
+    const float* __restrict__ part_b, const float* __restrict__ hyper, int mode,
+    float trust_coef, float wd, float* __restrict__ ratio, float* __restrict__ norms) {
+  if (hyper[HYPER_SKIP] != 0.f) return;
+  const int64_t* d = seg + (int64_t)blockIdx.x * SEG_COLS;
+  const int64_t first = d[SEG_FIRST];
+  int64_t cnt = d[SEG_NCHUNK];
+  if (first < 0 || cnt < 0 || first + cnt > nchunks) cnt = 0;
+  float a = 0.f, b = 0.f;
+  for (int64_t i = threadIdx.x; i < cnt; i += 256) {
+    a += part_p[first + i];
+    b += part_b[first + i];
+  }
+  block_sum2(a, b);
+  if (threadIdx.x != 0) return;
+  const int flags = (int)d[SEG_FLAGS];
+  const float pn = sqrtf(a), bn = sqrtf(b);
+  float r = 1.f;
+  if ((flags & SEG_ADAPT) && pn > 0.f && bn > 0.f) {
+    if (mode == TRUST_LARS) {
+      const float wd_s = (flags & SEG_DECAY) ? wd : 0.f;
+      r = trust_coef * pn / (bn + wd_s * pn + 1e-8f);
+    } else {
+      r = pn / bn;
+    }
+  }
+  ratio[blockIdx.x] = r;
+  norms[2 * blockIdx.x] = pn;
+  norms[2 * blockIdx.x + 1] = bn;
+}
+
+// LAMB stage 2 (p -= lr * ratio[s] * u, u from lamb_elem) and AdamW (ADAMW: torch's order,
+// p *= 1 - lr * wd_s, then adam_body's step; no ratio).  Both update m, v and write the
+// bf16 shadow.
+template <bool ADAMW>
+__global__ __launch_bounds__(256) void lamb_step_kernel(
+    float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+    float* __restrict__ v, bf16_t* __restrict__ shadow, int64_t n,
+    const float* __restrict__ step, const float* __restrict__ hyper,
+    const int64_t* __restrict__ seg, const int* __restrict__ chunk_seg, int nseg,
+    const float* __restrict__ ratio, float b1, float b2, float eps, float wd) {
+  if (hyper[HYPER_SKIP] != 0.f) return;
+  const Chunk k = chunk_of(seg, chunk_seg, nseg, blockIdx.x, n);
+  const AdamCoef c = adam_coef(step, b1, b2, eps);
+  const float lr = hyper[HYPER_LR], gs = hyper[HYPER_SCALE];
+  const float wd_s = (k.flags & SEG_DECAY) ? wd : 0.f;
+  const float step_size = lr / c.bc1;
+  const float keep = 1.f - lr * wd_s;
+  const float lr_r = ADAMW ? lr : lr * ratio[k.seg];
+  float4* __restrict__ p4 = (float4*)(p + k.off);
+  const float4* __restrict__ g4 = (const float4*)(g + k.off);
+  float4* __restrict__ m4 = (float4*)(m + k.off);
+  float4* __restrict__ v4 = (float4*)(v + k.off);
+  uint2* __restrict__ s2 = shadow ? (uint2*)(shadow + k.off) : nullptr;
+  for (int i = threadIdx.x; i < k.n4; i += 256) {
+    float4 pp = p4[i];
+    const float4 gg = g4[i];
+    float4 mm = m4[i];
+    float4 vv = v4[i];
+    float* pf = (float*)&pp;
+    const float* gf = (const float*)&gg;
+    float* mf = (float*)&mm;
+    float* vf = (float*)&vv;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      if (ADAMW) {
+        moments_elem(gf[j], gs, mf[j], vf[j], c);
+        const float denom = sqrtf(vf[j]) / c.bc2s + c.eps;
+        pf[j] *= keep;
+        pf[j] -= step_size * mf[j] / denom;
+      } else {
+        const float uu = lamb_elem(pf[j], gf[j], gs, mf[j], vf[j], wd_s, c);
+        pf[j] -= lr_r * uu;
+      }
+    }
+    p4[i] = pp;
+    m4[i] = mm;
+    v4[i] = vv;
+    if (s2) s2[i] = make_uint2(pack2(pf[0], pf[1]), pack2(pf[2], pf[3]));
+  }
+}
+
+// LARS: g' = ratio[s] * (g^ + wd_s * p), then sgd_body's momentum rule with wd = 0 (first
+// step seeds the buffer; dampening; nesterov); writes the bf16 shadow
+__global__ __launch_bounds__(256) void lars_step_kernel(
+    float* __restrict__ p, const float* __restrict__ g, float* __restrict__ buf,
+    bf16_t* __restrict__ shadow, int64_t n, const float* __restrict__ step,
+    const float* __restrict__ hyper, const int64_t* __restrict__ seg,
+    const int* __restrict__ chunk_seg, int nseg, const float* __restrict__ ratio,
+    float momentum, float dampening, float wd, int nesterov) {
+  if (hyper[HYPER_SKIP] != 0.f) return;
+  const Chunk k = chunk_of(seg, chunk_seg, nseg, blockIdx.x, n);
+  const bool first = step[0] == 0.f;
+  const float lr = hyper[HYPER_LR], gs = hyper[HYPER_SCALE];
+  const float wd_s = (k.flags & SEG_DECAY) ? wd : 0.f;
+  const float r = ratio[k.seg];
+  float4* __restrict__ p4 = (float4*)(p + k.off);
+  const float4* __restrict__ g4 = (const float4*)(g + k.off);
+  float4* __restrict__ b4 = (float4*)(buf + k.off);
+  uint2* __restrict__ s2 = shadow ? (uint2*)(shadow + k.off) : nullptr;
+  for (int i = threadIdx.x; i < k.n4; i += 256) {
+    float4 pp = p4[i];
+    const float4 gg = g4[i];
+    float4 bb = b4[i];
+    float* pf = (float*)&pp;
+    const float* gf = (const float*)&gg;
+    float* bf = (float*)&bb;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      float gr = r * (gf[j] * gs + wd_s * pf[j]);
+      if (momentum != 0.f) {
+        bf[j] = first ? gr : momentum * bf[j] + (1.f - dampening) * gr;
+        gr = nesterov ? gr + momentum * bf[j] : bf[j];
+      }
+      pf[j] -= lr * gr;
+    }
+    p4[i] = pp;
+    if (momentum != 0.f) b4[i] = bb;
+    if (s2) s2[i] = make_uint2(pack2(pf[0], pf[1]), pack2(pf[2], pf[3]));
+  }
+}
+
+int seg_chunk() { return SEG_CHUNK; }
+
+void seg_sqnorm(const float* x, int64_t n, const int64_t* seg, const int* chunk_seg, int nseg,
+                int nchunks, const float* hyper, int scaled, float* part, hipStream_t s) {
+  if (nchunks <= 0) return;
+  hipLaunchKernelGGL(seg_sqnorm_kernel, dim3(nchunks), dim3(256), 0, s, x, n, seg, chunk_seg,
+                     nseg, hyper, scaled, part);
+}
+
+void lamb_norms(const float* p, const float* g, const float* m, const float* v, int64_t n,
+                const float* step, const float* hyper, const int64_t* seg, const int* chunk_seg,
+                int nseg, int nchunks, float* part_p, float* part_u, float b1, float b2,
+                float eps, float wd, hipStream_t s) {
+  if (nchunks <= 0) return;
+  hipLaunchKernelGGL(lamb_norms_kernel, dim3(nchunks), dim3(256), 0, s, p, g, m, v, n, step,
+                     hyper, seg, chunk_seg, nseg, part_p, part_u, b1, b2, eps, wd);
+}
+
+void trust_ratio(const int64_t* seg, int nseg, int nchunks, const float* part_p,
+                 const float* part_b, const float* hyper, int mode, float trust_coef, float wd,
+                 float* ratio, float* norms, hipStream_t s) {
+  if (nseg <= 0) return;
+  hipLaunchKernelGGL(trust_ratio_kernel, dim3(nseg), dim3(256), 0, s, seg, nchunks, part_p,
+                     part_b, hyper, mode, trust_coef, wd, ratio, norms);
+}
+
+void lamb_step_dev(float* p, const float* g, float* m, float* v, bf16_raw* shadow, int64_t n,
+                   const float* step, const float* hyper, const int64_t* seg,
+                   const int* chunk_seg, int nseg, int nchunks, const float* ratio, float b1,
+                   float b2, float eps, float wd, int adamw, hipStream_t s) {
+  if (nchunks <= 0) return;
+  if (adamw)
+    hipLaunchKernelGGL(lamb_step_kernel<true>, dim3(nchunks), dim3(256), 0, s, p, g, m, v,
+                       shadow, n, step, hyper, seg, chunk_seg, nseg, ratio, b1, b2, eps, wd);
+  else
+    hipLaunchKernelGGL(lamb_step_kernel<false>, dim3(nchunks), dim3(256), 0, s, p, g, m, v,
+                       shadow, n, step, hyper, seg, chunk_seg, nseg, ratio, b1, b2, eps, wd);
+}
+
+void lars_step_dev(float* p, const float* g, float* buf, bf16_raw* shadow, int64_t n,
+                   const float* step, const float* hyper, const int64_t* seg,
+                   const int* chunk_seg, int nseg, int nchunks, const float* ratio,
+                   float momentum, float dampening, float wd, int nesterov, hipStream_t s) {
+  if (nchunks <= 0) return;
+  hipLaunchKernelGGL(lars_step_kernel, dim3(nchunks), dim3(256), 0, s, p, g, buf, shadow, n,
+                     step, hyper, seg, chunk_seg, nseg, ratio, momentum, dampening, wd,
+                     nesterov);
+}
+
 static void step_inc_launch(float* step, hipStream_t s);
 
 // ------------------------------------------------------------ transposed weight shadow

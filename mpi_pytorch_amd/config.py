@@ -60,9 +60,12 @@ class Config:
     synthetic: bool = True                 # synthetic images (no Herbarium data offline)
     synthetic_images: int = 0              # images per epoch in synthetic mode (0 => 800 like DEBUG)
     image_size: int = 0                    # 0 => use WIDTH/HEIGHT
-    optimizer: str = "adam"                # adam | sgd
+    optimizer: str = "adam"                # adam | sgd | adamw | lamb | lars
     momentum: float = 0.9
-    weight_decay: float = 0.0
+    weight_decay: float = 0.0              # adam | sgd: coupled L2; adamw | lamb | lars: decoupled
+    trust_coef: float = 0.001              # lars: the trust ratio's coefficient
+    wd_exclude_1d: bool = True             # adamw | lamb | lars: no decay / trust ratio on 1-D
+                                           # parameters (BN, biases); adam | sgd decay everything
     # training recipe on the device (optim.py; all off by default = the reference's recipe)
     lr_schedule: str = "constant"          # constant | cosine | step (after the warm-up)
     warmup_steps: int = 0                  # linear warm-up: lr * (k + 1) / warmup_steps
@@ -107,8 +110,10 @@ class Config:
         if self.MODEL_NAME not in MODEL_NAMES:
             raise ValueError("Invalid model name {!r}; expected one of {}".format(
                 self.MODEL_NAME, MODEL_NAMES))
-        if self.optimizer not in ("adam", "sgd"):
-            raise ValueError("optimizer must be adam|sgd")
+        if self.optimizer not in ("adam", "sgd", "adamw", "lamb", "lars"):
+            raise ValueError("optimizer must be adam|sgd|adamw|lamb|lars")
+        if not self.trust_coef > 0.0:
+            raise ValueError("trust_coef must be > 0")
         if self.lr_schedule not in ("constant", "cosine", "step"):
             raise ValueError("lr_schedule must be constant|cosine|step")
         if self.warmup_steps < 0 or self.lr_decay_steps < 0:

@@ -385,14 +385,18 @@ def build_training(name: str, num_classes: int, device, world: World, lr: float,
                    feature_extract: bool = False, bucket_mb: float = 16.0, overlap: bool = True,
                    comm_dtype: str = "fp32", comm_ctas: Optional[int] = None,
                    schedule: Optional[dict] = None, clip_grad_norm: float = 0.0,
-                   label_smoothing: float = 0.0):
+                   label_smoothing: float = 0.0, trust_coef: float = 0.001,
+                   wd_exclude_1d: bool = True):
     """``schedule``: keyword arguments of ``optim.set_schedule`` (None: constant LR);
     ``clip_grad_norm`` > 0: global-norm gradient clipping (``optim.set_clip``);
-    ``label_smoothing``: the training loss's label smoothing in [0, 1]."""
+    ``label_smoothing``: the training loss's label smoothing in [0, 1];
+    ``trust_coef`` / ``wd_exclude_1d``: the layer-wise optimizers' settings (adamw | lamb |
+    lars only)."""
     model, input_size = build_model(name, num_classes, feature_extract, device, world,
                                     bucket_mb=bucket_mb, overlap=overlap, comm_dtype=comm_dtype,
                                     comm_ctas=comm_ctas)
-    opt = build_optimizer(optimizer, model, lr, momentum, weight_decay)
+    opt = build_optimizer(optimizer, model, lr, momentum, weight_decay, trust_coef,
+                          wd_exclude_1d)
     if schedule is not None:
         opt.set_schedule(**schedule)
     if clip_grad_norm > 0.0:

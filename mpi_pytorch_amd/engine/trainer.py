@@ -223,7 +223,8 @@ def run_training(cfg: Config) -> dict:
         cfg.weight_decay, cfg.FEATURE_EXTRACT, cfg.bucket_mb, cfg.overlap_comm,
         cfg.grad_comm_dtype, None if cfg.grad_comm_ctas < 0 else cfg.grad_comm_ctas,
         schedule=schedule, clip_grad_norm=cfg.clip_grad_norm,
-        label_smoothing=cfg.label_smoothing)
+        label_smoothing=cfg.label_smoothing, trust_coef=cfg.trust_coef,
+        wd_exclude_1d=cfg.wd_exclude_1d)
     log.info("_Model Created: {}".format(cfg.MODEL_NAME))
     spec = input_spec(model, out_hw)
     for ld in (train_loader, val_loader):
@@ -289,6 +290,10 @@ def run_training(cfg: Config) -> dict:
             rec["lr"] = opt.current_lr()
             rec["grad_norm"] = opt.last_grad_norm() if cfg.clip_grad_norm > 0.0 else None
             rec["nonfinite_steps"] = opt.nonfinite_steps()
+        if getattr(opt, "trust_mode", None) is not None:  # lamb | lars (one sync)
+            tr = sorted(opt.last_trust_ratios().values())
+            if tr:
+                rec["trust_ratio"] = {"min": tr[0], "median": tr[len(tr) // 2], "max": tr[-1]}
         if step.timer is not None:
             rec["phases_ms"] = step.timer.summary()
         if size > 1:

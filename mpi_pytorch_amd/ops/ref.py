@@ -712,6 +712,144 @@ def sgd_step_dev(master, grad, buf, shadow, step_t, hyper, momentum, dampening, 
              nesterov, float(hyper[HYPER_SCALE]))
 
 
+# ---- layer-wise optimizers on the segment plan (AdamW / LAMB / LARS); csrc/kernels/optim.hip
+# seg [nseg][SEG_COLS] int64 rows (csrc/kernels/api.h SEG_*); the segments tile [0, n)
+SEG_OFF, SEG_LEN, SEG_FIRST, SEG_NCHUNK, SEG_FLAGS = range(5)
+SEG_COLS = 5
+SEG_DECAY, SEG_ADAPT = 1, 2
+TRUST_LAMB, TRUST_LARS = 0, 1
+
+
+def seg_chunk():
+    return 16384
+
+
+def _seg_total(seg):
+    rows = seg.tolist()
+    off = 0
+    for r in rows:  # (the twins expand per-segment values over a gap-free tiling)
+        assert r[SEG_OFF] == off and r[SEG_LEN] > 0, "segments must tile [0, n)"
+        off += r[SEG_LEN]
+    return rows, off
+
+
+def _per_element(seg, vals, like):
+    """vals[s] repeated over segment s: one value per arena element."""
+    return torch.repeat_interleave(torch.as_tensor(vals, dtype=like.dtype, device=like.device),
+                                   seg[:, SEG_LEN].to(like.device))
+
+
+def _chunk_sums(sq, rows, part):
+    """part[c] = float64 sum of the per-element values ``sq`` over chunk c."""
+    CH = seg_chunk()
+    for off, ln, first, nch, _flags in rows:
+        t = sq[off:off + ln]
+        if ln % CH:
+            t = torch.nn.functional.pad(t, (0, CH - ln % CH))
+        part[first:first + nch] = t.view(-1, CH).sum(1).to(part.dtype)
+
+
+def seg_sqnorm(x, seg, chunk_seg, hyper, scaled, part):
+    """Per-chunk sum of squares of an arena-shaped buffer, accumulated in float64."""
+    if float(hyper[HYPER_SKIP]) != 0.0:
+        return
+    rows, n = _seg_total(seg)
+    xs = x[:n].double()
+    if scaled:
+        xs = xs * float(hyper[HYPER_SCALE])
+    _chunk_sums(xs * xs, rows, part)
+
+
+def _lamb_u(p, g, m, v, step_t, gs, b1, b2, eps, wd_e):
+    """New moments and LAMB's update direction u = m^ / (sqrt(v^) + eps) + wd * p, in the
+    dtype of the inputs (``wd_e``: per-element decay or None)."""
+    step = float(step_t.item()) + 1.0
+    gr = g * gs
+    m2 = m.mul(b1).add_(gr, alpha=1 - b1)  # (adam_step's operations: the same moments)
+    v2 = v.mul(b2).addcmul_(gr, gr, value=1 - b2)
+    u = (m2 / (1 - b1 ** step)) / (v2.sqrt() / math.sqrt(1 - b2 ** step) + eps)
+    if wd_e is not None:
+        u = u + wd_e * p
+    return m2, v2, u
+
+
+def _decay_per_element(seg, rows, wd, like):
+    if wd == 0.0:
+        return None
+    return _per_element(seg, [wd if r[SEG_FLAGS] & SEG_DECAY else 0.0 for r in rows], like)
+
+
+def lamb_norms(master, grad, m, v, step_t, hyper, seg, chunk_seg, part_p, part_u, b1, b2, eps,
+               wd):
+    """LAMB stage 1: per-chunk sums of p^2 and of u^2 (float64 accumulation); reads only."""
+    if float(hyper[HYPER_SKIP]) != 0.0:
+        return
+    rows, n = _seg_total(seg)
+    p = master[:n]
+    _m, _v, u = _lamb_u(p, grad[:n], m[:n], v[:n], step_t, float(hyper[HYPER_SCALE]), b1, b2,
+                        eps, _decay_per_element(seg, rows, wd, p))
+    _chunk_sums(p.double() ** 2, rows, part_p)
+    _chunk_sums(u.double() ** 2, rows, part_u)
+
+
+def trust_ratio(seg, chunk_seg, part_p, part_b, hyper, mode, trust_coef, wd, ratio, norms):
+    if float(hyper[HYPER_SKIP]) != 0.0:
+        return
+    nv = norms.view(-1)
+    for s, (_off, _ln, first, nch, flags) in enumerate(seg.tolist()):
+        pn = math.sqrt(float(part_p[first:first + nch].double().sum()))
+        bn = math.sqrt(float(part_b[first:first + nch].double().sum()))
+        r = 1.0
+        if flags & SEG_ADAPT and pn > 0.0 and bn > 0.0:
+            if mode == TRUST_LARS:
+                r = trust_coef * pn / (bn + (wd if flags & SEG_DECAY else 0.0) * pn + 1e-8)
+            else:
+                r = pn / bn
+        ratio[s] = r
+        nv[2 * s] = pn
+        nv[2 * s + 1] = bn
+
+
+def lamb_step_dev(master, grad, m, v, shadow, step_t, hyper, seg, chunk_seg, ratio, b1, b2, eps,
+                  wd, adamw):
+    """LAMB stage 2, or torch.optim.AdamW's rule with a per-segment decay (``adamw``)."""
+    if float(hyper[HYPER_SKIP]) != 0.0:
+        return
+    rows, n = _seg_total(seg)
+    lr, gs = float(hyper[HYPER_LR]), float(hyper[HYPER_SCALE])
+    p = master[:n]
+    wd_e = _decay_per_element(seg, rows, wd, p)
+    if adamw:
+        if wd_e is not None:
+            p.mul_(1 - lr * wd_e)
+        adam_step(p, grad[:n], m[:n], v[:n], None, step_t, lr, b1, b2, eps, 0.0, gs)
+    else:
+        m2, v2, u = _lamb_u(p, grad[:n], m[:n], v[:n], step_t, gs, b1, b2, eps, wd_e)
+        m[:n].copy_(m2)
+        v[:n].copy_(v2)
+        p.sub_(_per_element(seg, ratio[:len(rows)].tolist(), p) * lr * u)
+    if _opt(shadow) is not None:
+        shadow[:n].copy_(p)
+
+
+def lars_step_dev(master, grad, buf, shadow, step_t, hyper, seg, chunk_seg, ratio, momentum,
+                  dampening, wd, nesterov):
+    """g' = ratio[s] * (g^ + wd_s * p), then sgd_step's momentum rule with wd = 0."""
+    if float(hyper[HYPER_SKIP]) != 0.0:
+        return
+    rows, n = _seg_total(seg)
+    p = master[:n]
+    g = grad[:n] * float(hyper[HYPER_SCALE])
+    wd_e = _decay_per_element(seg, rows, wd, p)
+    if wd_e is not None:
+        g = g + wd_e * p
+    g = g * _per_element(seg, ratio[:len(rows)].tolist(), p)
+    sgd_step(p, g, buf[:n], None, step_t, float(hyper[HYPER_LR]), momentum, dampening, 0.0,
+             nesterov, 1.0)
+    if _opt(shadow) is not None:
+        shadow[:n].copy_(p)
+
+
 # ------------------------------------------------------------------------ preprocessing
 def preprocess(img_u8, oh, ow, mean, std, mode, cpad, out_dtype, pad=None, extents=None,
                boxes=None):

@@ -35,6 +35,15 @@ grad_scale * sqrt(sum g^2)`` over the trainable arena, ``coef = min(1, max_norm 
 is inf / NaN is skipped - weights, moments and bf16 shadow stay bitwise unchanged and the
 device counter ``nonfinite_steps`` goes up - but ``step_t`` still advances: a skipped step
 counts for the schedule and for Adam's bias correction.
+
+Layer-wise optimizers (beyond the reference): ``FusedAdamW`` (decoupled weight decay),
+``FusedLAMB`` and ``FusedLARS`` (a per-parameter trust ratio) run on a segment and chunk
+plan over the arena (``build_segment_plan``) that tells the kernels which parameter an
+element belongs to.  Per-parameter norms are fixed-order sums (no float atomics), so they
+are bitwise reproducible and equal on every data-parallel rank.  These optimizers always go
+through the hyper record, and by default (``wd_exclude_1d``) 1-D parameters - BN scale and
+shift, biases - get no weight decay and a trust ratio of 1.  ``adam`` and ``sgd`` are
+unchanged: coupled L2 decay on every element.
 """
 from __future__ import annotations
 
@@ -166,6 +175,10 @@ class _FlatOptimizer:
 
     def _recipe_step(self) -> None:
         """norm (only with clipping) -> hyper record -> device-argument update."""
+        self._hyper_step()
+        self._update_dev(0, self.arena.n_train)
+
+    def _hyper_step(self) -> None:
         n = self.arena.n_train
         k = self._kernel()
         nparts = 0
@@ -178,7 +191,6 @@ class _FlatOptimizer:
                        float(sc["warmup_steps"]), float(sc["total_steps"]),
                        float(sc["lr_min_ratio"]), float(sc["gamma"]), float(sc["decay_steps"]),
                        float(self._max_norm), float(self.grad_scale))
-        self._update_dev(0, n)
 
     def step(self) -> None:
         if self.arena.n_train == 0:
@@ -353,12 +365,203 @@ class FusedSGD(_FlatOptimizer):
         return 1.0
 
 
+# ------------------------------------------------------- layer-wise: AdamW / LAMB / LARS
+def build_segment_plan(arena: ParamArena, wd_exclude_1d: bool = True,
+                       chunk: Optional[int] = None):
+    """The segment and chunk plan of ``arena``'s trainable region, as CPU tensors.
+
+    ``seg`` [nseg][5] int64 = (offset, aligned length, first chunk, chunk count, flags):
+    segment ``s`` is the aligned slice of ``arena.trainable[s]`` (grouped parameters stay
+    one segment each), so the segments tile ``[0, n_train)`` and start on ``ALIGN``
+    boundaries.  ``chunk_seg`` [nchunks] int32: each segment is cut into consecutive chunks
+    of at most ``chunk`` elements (the kernels' ``seg_chunk()``), none crossing a segment.
+    Flags: ``SEG_DECAY`` (weight decay applies) and ``SEG_ADAPT`` (a trust ratio applies);
+    with ``wd_exclude_1d`` parameters stored with ``ndim <= 1`` (BN scale / shift, biases -
+    a ``pad_out`` bias is still 1-D) get neither."""
+    from .parallel.arena import _align
+    chunk = int(_ref.seg_chunk() if chunk is None else chunk)
+    rows, chunk_seg, off = [], [], 0
+    for s, p in enumerate(arena.trainable):
+        assert arena.offsets[id(p)] == off, "trainable parameters must tile the arena"
+        ln = _align(p.numel())
+        nch = (ln + chunk - 1) // chunk
+        flags = 0 if (wd_exclude_1d and p.ndim <= 1) else _ref.SEG_DECAY | _ref.SEG_ADAPT
+        rows.append([off, ln, len(chunk_seg), nch, flags])
+        chunk_seg.extend([s] * nch)
+        off += ln
+    assert off == arena.n_train
+    seg = torch.tensor(rows, dtype=torch.int64).reshape(-1, _ref.SEG_COLS)
+    return seg, torch.tensor(chunk_seg, dtype=torch.int32)
+
+
+class _Layerwise:
+    """Mixin over a flat optimizer: the segment plan, per-parameter fixed-order norms and
+    trust ratios, and the ``step()`` that always goes through the hyper record.
+
+    ``step()``: ``grad_sqnorm`` (only with clipping) -> ``hyper_update`` -> norms ->
+    ``trust_ratio`` -> update -> ``refresh_transposed(step_inc=...)``.  Plan, partials,
+    ratios and norms are tensor attributes, so ``TrainStep`` snapshots and restores them
+    around graph capture with the rest of the optimizer state."""
+    trust_mode: Optional[int] = None  # ref.TRUST_LAMB | ref.TRUST_LARS | None (no ratio)
+
+    def _init_plan(self, trust_coef: float, wd_exclude_1d: bool) -> None:
+        self.trust_coef = float(trust_coef)
+        self.wd_exclude_1d = bool(wd_exclude_1d)
+        dev = self.arena.device
+        k = self._kernel()
+        seg, chunk_seg = build_segment_plan(self.arena, self.wd_exclude_1d, int(k.seg_chunk()))
+        self.plan_seg = seg.to(dev)
+        self.plan_chunk_seg = chunk_seg.to(dev)
+        nseg, nch = seg.shape[0], chunk_seg.numel()
+        # the CPU twins accumulate (and keep) the norms' partials in float64
+        pt = torch.float32 if dev.type == "cuda" else torch.float64
+        self.seg_part = torch.zeros(2, max(nch, 1), dtype=pt, device=dev)
+        self.seg_ratio = torch.ones(max(nseg, 1), dtype=torch.float32, device=dev)
+        self.seg_norms = torch.zeros(max(nseg, 1), 2, dtype=torch.float32, device=dev)
+        self._ensure_record()
+
+    def _layerwise_update(self, n: int) -> None:
+        raise NotImplementedError
+
+    def _trust_ratio(self) -> None:
+        g = self.param_groups[0]
+        self._kernel().trust_ratio(self.plan_seg, self.plan_chunk_seg, self.seg_part[0],
+                                   self.seg_part[1], self.hyper, int(self.trust_mode),
+                                   float(self.trust_coef), float(g["weight_decay"]),
+                                   self.seg_ratio, self.seg_norms)
+
+    def step(self) -> None:
+        n = self.arena.n_train
+        if n == 0:
+            return
+        self._hyper_step()
+        self._layerwise_update(n)
+        self.arena.refresh_transposed(step_inc=self.step_t)
+
+    def last_trust_ratios(self) -> Dict[str, float]:
+        """{parameter name: trust ratio of the last update} (1.0 before any update, for
+        parameters without a ratio, and always for AdamW); one host sync."""
+        r = self.seg_ratio.cpu().tolist()
+        a = self.arena
+        return {a.names[id(p)]: r[s] for s, p in enumerate(a.trainable)}
+
+    def last_param_norms(self) -> Dict[str, tuple]:
+        """{parameter name: (|p|, |u| or |g^|)} of the last update's norms (one sync)."""
+        nv = self.seg_norms.cpu().tolist()
+        a = self.arena
+        return {a.names[id(p)]: tuple(nv[s]) for s, p in enumerate(a.trainable)}
+
+    def state_dict(self) -> Dict:
+        sd = super().state_dict()
+        g = sd["param_groups"][0]
+        g["mpa_trust_coef"] = float(self.trust_coef)
+        g["mpa_wd_exclude_1d"] = bool(self.wd_exclude_1d)
+        return sd
+
+    def load_state_dict(self, sd: Dict) -> None:
+        g = sd["param_groups"][0]
+        super().load_state_dict(sd)
+        self.trust_coef = float(g.get("mpa_trust_coef", self.trust_coef))
+        ex = bool(g.get("mpa_wd_exclude_1d", self.wd_exclude_1d))
+        if ex != self.wd_exclude_1d:  # the flags are part of the plan: rebuild it in place
+            self.wd_exclude_1d = ex
+            seg, _ = build_segment_plan(self.arena, ex, int(self._kernel().seg_chunk()))
+            self.plan_seg.copy_(seg)
+
+
+class FusedAdamW(_Layerwise, FusedAdam):
+    """``torch.optim.AdamW``: decoupled weight decay, by default not on 1-D parameters."""
+    kind = "adamw"
+
+    def __init__(self, params, arena: ParamArena, lr=1e-3, betas=(0.9, 0.999), eps=1e-8,
+                 weight_decay=1e-2, trust_coef=0.001, wd_exclude_1d=True):
+        FusedAdam.__init__(self, params, arena, lr=lr, betas=betas, eps=eps,
+                           weight_decay=weight_decay)
+        self._init_plan(trust_coef, wd_exclude_1d)
+
+    def _group_defaults(self):
+        d = FusedAdam._group_defaults(self)
+        d["decoupled_weight_decay"] = True
+        return d
+
+    def _adam_args(self):
+        g = self.param_groups[0]
+        b1, b2 = g["betas"]
+        return float(b1), float(b2), float(g["eps"]), float(g["weight_decay"])
+
+    def _step_kernel(self, n: int, adamw: bool) -> None:
+        a, sh = self.arena, self._shadow()
+        self._kernel().lamb_step_dev(a.master[:n], a.grad[:n], self.exp_avg[:n],
+                                     self.exp_avg_sq[:n], sh[:n] if sh.numel() else sh,
+                                     self.step_t, self.hyper, self.plan_seg,
+                                     self.plan_chunk_seg, self.seg_ratio, *self._adam_args(),
+                                     adamw)
+
+    def _layerwise_update(self, n: int) -> None:
+        self._step_kernel(n, True)
+
+
+class FusedLAMB(FusedAdamW):
+    """LAMB (You et al. 2020, with bias correction): Adam's direction plus decoupled decay,
+    scaled per parameter by ``|p| / |u|``.  Stage 1 norms the update the step would apply,
+    stage 2 recomputes and applies it: no update buffer, the gradient arena stays intact."""
+    kind = "lamb"
+    trust_mode = _ref.TRUST_LAMB
+
+    def _layerwise_update(self, n: int) -> None:
+        a = self.arena
+        self._kernel().lamb_norms(a.master[:n], a.grad[:n], self.exp_avg[:n],
+                                  self.exp_avg_sq[:n], self.step_t, self.hyper, self.plan_seg,
+                                  self.plan_chunk_seg, self.seg_part[0], self.seg_part[1],
+                                  *self._adam_args())
+        self._trust_ratio()
+        self._step_kernel(n, False)
+
+
+class FusedLARS(_Layerwise, FusedSGD):
+    """LARS (You et al. 2017) on SGD-momentum: per parameter ``g' = ratio * (g^ + wd * p)``
+    with ``ratio = trust_coef * |p| / (|g^| + wd * |p| + 1e-8)``, ``g^`` the averaged,
+    clipped gradient."""
+    kind = "lars"
+    trust_mode = _ref.TRUST_LARS
+
+    def __init__(self, params, arena: ParamArena, lr=0.1, momentum=0.9, dampening=0.0,
+                 weight_decay=0.0, nesterov=False, trust_coef=0.001, wd_exclude_1d=True):
+        FusedSGD.__init__(self, params, arena, lr=lr, momentum=momentum, dampening=dampening,
+                          weight_decay=weight_decay, nesterov=nesterov)
+        self._init_plan(trust_coef, wd_exclude_1d)
+
+    def _layerwise_update(self, n: int) -> None:
+        a, k, g, sh = self.arena, self._kernel(), self.param_groups[0], self._shadow()
+        k.seg_sqnorm(a.master[:n], self.plan_seg, self.plan_chunk_seg, self.hyper, False,
+                     self.seg_part[0])
+        k.seg_sqnorm(a.grad[:n], self.plan_seg, self.plan_chunk_seg, self.hyper, True,
+                     self.seg_part[1])
+        self._trust_ratio()
+        k.lars_step_dev(a.master[:n], a.grad[:n], self.momentum_buffer[:n],
+                        sh[:n] if sh.numel() else sh, self.step_t, self.hyper, self.plan_seg,
+                        self.plan_chunk_seg, self.seg_ratio, float(g["momentum"]),
+                        float(g["dampening"]), float(g["weight_decay"]), bool(g["nesterov"]))
+
+
+OPTIMIZERS = ("adam", "sgd", "adamw", "lamb", "lars")
+
+
 def build_optimizer(name: str, model: nn.Module, lr: float, momentum: float = 0.9,
-                    weight_decay: float = 0.0):
+                    weight_decay: float = 0.0, trust_coef: float = 0.001,
+                    wd_exclude_1d: bool = True):
+    """``trust_coef`` (LARS) and ``wd_exclude_1d`` apply to adamw | lamb | lars only."""
     arena = model._mpa_arena
     params = list(model.parameters())
     if name == "adam":
         return FusedAdam(params, arena, lr=lr, weight_decay=weight_decay)
     if name == "sgd":
         return FusedSGD(params, arena, lr=lr, momentum=momentum, weight_decay=weight_decay)
-    raise ValueError(name)
+    if name in ("adamw", "lamb"):
+        cls = FusedAdamW if name == "adamw" else FusedLAMB
+        return cls(params, arena, lr=lr, weight_decay=weight_decay, trust_coef=trust_coef,
+                   wd_exclude_1d=wd_exclude_1d)
+    if name == "lars":
+        return FusedLARS(params, arena, lr=lr, momentum=momentum, weight_decay=weight_decay,
+                         trust_coef=trust_coef, wd_exclude_1d=wd_exclude_1d)
+    raise ValueError("optimizer must be one of {}, got {!r}".format("|".join(OPTIMIZERS), name))

@@ -7,7 +7,12 @@ With ``--recipe`` also the training recipe's kernels at the same sizes: ``adam_s
 ``adam_step``, and the gradient-norm pass ``grad_sqnorm`` + ``hyper_update`` (4 bytes per
 parameter, read only).
 
-    python tools/adam_probe.py [--recipe]
+With ``--layerwise`` the optimizer phase of ``adam`` (the yardstick), ``adamw``, ``lamb``
+and ``lars`` on the segment plan of the ResNet-18 headline arena (64,500 classes), in one
+process: AdamW moves Adam's 30 bytes per parameter, LAMB 46 (stage 1 reads p, g, m, v again),
+LARS 30 against SGD-momentum's 22 (two norm passes).
+
+    python tools/adam_probe.py [--recipe | --layerwise]
 """
 import sys
 
@@ -32,9 +37,68 @@ def _time(fn, flush, cold, iters=12):
     return ts[len(ts) // 2], ts[0], ts[-1]
 
 
+def layerwise(k, dev, flush):
+    from mpi_pytorch_amd.models import initialize_model
+    from mpi_pytorch_amd.optim import build_segment_plan
+    from mpi_pytorch_amd.parallel.arena import ParamArena
+    arena = ParamArena(initialize_model("resnet18", 64500, False, False)[0], torch.device("cpu"),
+                       shadow=False)
+    seg, chunk_seg = build_segment_plan(arena, True, int(k.seg_chunk()))
+    n = arena.n_train
+    print("resnet18 / 64,500 classes: %d elements, %d segments, %d chunks of <= %d"
+          % (n, seg.shape[0], chunk_seg.numel(), k.seg_chunk()), flush=True)
+    seg, chunk_seg = seg.to(dev), chunk_seg.to(dev)
+    p = torch.randn(n, device=dev)
+    g = torch.randn(n, device=dev) * 1e-2
+    m = torch.zeros(n, device=dev)
+    v = torch.zeros(n, device=dev)
+    sh = torch.empty(n, dtype=torch.bfloat16, device=dev)
+    st = torch.zeros(1, device=dev)
+    hyper = torch.zeros(8, device=dev)
+    hyper[0], hyper[1] = 1e-3, 1.0
+    part = torch.zeros(2, chunk_seg.numel(), device=dev)
+    ratio = torch.ones(seg.shape[0], device=dev)
+    norms = torch.zeros(seg.shape[0], 2, device=dev)
+
+    def adam():
+        k.adam_step_dev(p, g, m, v, sh, st, hyper, 0.9, 0.999, 1e-8, 0.0)
+
+    def adamw():
+        k.lamb_step_dev(p, g, m, v, sh, st, hyper, seg, chunk_seg, ratio, 0.9, 0.999, 1e-8, 0.01,
+                        True)
+
+    def lamb():
+        k.lamb_norms(p, g, m, v, st, hyper, seg, chunk_seg, part[0], part[1], 0.9, 0.999, 1e-8,
+                     0.01)
+        k.trust_ratio(seg, chunk_seg, part[0], part[1], hyper, 0, 0.0, 0.01, ratio, norms)
+        k.lamb_step_dev(p, g, m, v, sh, st, hyper, seg, chunk_seg, ratio, 0.9, 0.999, 1e-8, 0.01,
+                        False)
+
+    def sgd():
+        k.sgd_step_dev(p, g, m, sh, st, hyper, 0.9, 0.0, 0.0, False)
+
+    def lars():
+        k.seg_sqnorm(p, seg, chunk_seg, hyper, False, part[0])
+        k.seg_sqnorm(g, seg, chunk_seg, hyper, True, part[1])
+        k.trust_ratio(seg, chunk_seg, part[0], part[1], hyper, 1, 0.001, 0.01, ratio, norms)
+        k.lars_step_dev(p, g, m, sh, st, hyper, seg, chunk_seg, ratio, 0.9, 0.0, 0.01, False)
+
+    # (adam runs first and last: the spread between equal runs is the yardstick)
+    runs = [("adam", adam, 30), ("adamw", adamw, 30), ("lamb", lamb, 46), ("sgd", sgd, 22),
+            ("lars", lars, 30), ("adam", adam, 30)]
+    for cold in (False, True):
+        for name, fn, bpp in runs:
+            us, lo, hi = _time(fn, flush, cold)
+            print(f"{name:13s} n={n / 1e6:7.2f}M {'cold' if cold else 'warm'}: {us:8.1f} us "
+                  f"(min {lo:.1f}, max {hi:.1f})  {bpp * n / us / 1e6:6.2f} TB/s", flush=True)
+
+
 def main():
     recipe = "--recipe" in sys.argv[1:]
     k = _ext.load()
+    if "--layerwise" in sys.argv[1:]:
+        dev = torch.device("cuda:0")
+        return layerwise(k, dev, torch.empty(1 << 30, dtype=torch.float32, device=dev))
     dev = torch.device("cuda:0")
     flush = torch.empty(1 << 30, dtype=torch.float32, device=dev)
     for n in (11_689_512, 44_549_160, 138_357_544):

@@ -13,6 +13,7 @@ from collections import defaultdict
 CATS = [
     ("aten/runtime", r"at::native|__amd_rocclr"),
     ("optimizer", r"adam_kernel|sgd_kernel|adam_dev_kernel|sgd_dev_kernel|grad_sqnorm|sqnorm_sum|hyper_kernel|"
+                  r"seg_sqnorm|lamb_norms|trust_ratio|lamb_step|lars_step|"
                   r"transpose_krsc|zero_f32|step_inc"),
     ("conv wgrad", r"wgrad|splitk_finalize"),
     ("conv (stem)", r"conv_stem"),
