@@ -1262,17 +1262,48 @@ static float check_smoothing(double smoothing) {
   return (float)smoothing;
 }
 
-std::vector<Tensor> ce_fwd(Tensor logits, Tensor labels, double smoothing) {
+// The second label and its weight of a mixed batch (Mixup / CutMix): labels2 int64 [B] and
+// lam float32 [B] on the logits' device, contiguous, both or neither.  lam stays a device
+// array (never a host scalar), so a captured graph replays with new values.
+struct MixLabels {
+  const int64_t* labels2 = nullptr;
+  const float* lam = nullptr;
+};
+
+static MixLabels check_mix_labels(const Tensor& logits, const c10::optional<Tensor>& labels2,
+                                  const c10::optional<Tensor>& lam) {
+  const bool has2 = labels2 && labels2->defined(), hasl = lam && lam->defined();
+  TORCH_CHECK(has2 == hasl, "cross-entropy: labels2 and lam go together");
+  MixLabels m;
+  if (!has2) return m;
+  const int64_t B = logits.size(0);
+  TORCH_CHECK(labels2->scalar_type() == torch::kInt64 && labels2->dim() == 1 &&
+                  labels2->size(0) == B,
+              "cross-entropy: labels2 must be int64 [B]");
+  TORCH_CHECK(lam->scalar_type() == torch::kFloat32 && lam->dim() == 1 && lam->size(0) == B,
+              "cross-entropy: lam must be float32 [B]");
+  TORCH_CHECK(labels2->device() == logits.device() && lam->device() == logits.device(),
+              "cross-entropy: labels2 / lam on another device");
+  TORCH_CHECK(labels2->is_contiguous() && lam->is_contiguous(),
+              "cross-entropy: labels2 / lam must be contiguous");
+  m.labels2 = labels2->data_ptr<int64_t>();
+  m.lam = lam->data_ptr<float>();
+  return m;
+}
+
+std::vector<Tensor> ce_fwd(Tensor logits, Tensor labels, double smoothing,
+                           c10::optional<Tensor> labels2, c10::optional<Tensor> lam) {
   const int ld = logits_ld(logits);
   const float eps = check_smoothing(smoothing);
   CHECK_CUDA(labels);
   TORCH_CHECK(labels.scalar_type() == torch::kInt64, "labels must be int64");
+  const MixLabels mx = check_mix_labels(logits, labels2, lam);
   const int B = logits.size(0), NC = logits.size(1);
   const c10::OptionalDeviceGuard g(device_of(logits));
   Tensor buf = torch::empty({1 + B}, logits.options().dtype(torch::kFloat32));
   Tensor lse = torch::empty({B}, logits.options().dtype(torch::kFloat32));
   mpa::ce_fwd(bp(logits), labels.contiguous().data_ptr<int64_t>(), B, NC, ld,
-              buf.data_ptr<float>(), lse.data_ptr<float>(), cur_stream(), eps);
+              buf.data_ptr<float>(), lse.data_ptr<float>(), cur_stream(), eps, mx.labels2, mx.lam);
   return {buf.narrow(0, 0, 1), lse};
 }
 
@@ -1281,11 +1312,13 @@ std::vector<Tensor> ce_fwd(Tensor logits, Tensor labels, double smoothing) {
 // out[0] = (or +=, accumulate) weight * mean CE and acc[0] += the same (acc optional);
 // returns the per-row log-sum-exp for the backward
 Tensor ce_fwd_weighted(Tensor logits, Tensor labels, Tensor out, Tensor acc, double weight,
-                       bool accumulate, double smoothing) {
+                       bool accumulate, double smoothing, c10::optional<Tensor> labels2,
+                       c10::optional<Tensor> lam) {
   const int ld = logits_ld(logits);
   const float eps = check_smoothing(smoothing);
   CHECK_CUDA(labels);
   TORCH_CHECK(labels.scalar_type() == torch::kInt64, "labels must be int64");
+  const MixLabels mx = check_mix_labels(logits, labels2, lam);
   CHECK_CUDA(out);
   CHECK_F32(out);
   TORCH_CHECK(out.numel() >= 1, "ce_fwd_weighted: out must hold one float");
@@ -1296,19 +1329,21 @@ Tensor ce_fwd_weighted(Tensor logits, Tensor labels, Tensor out, Tensor acc, dou
   Tensor lse = torch::empty({B}, logits.options().dtype(torch::kFloat32));
   mpa::ce_fwd_weighted(bp(logits), labels.contiguous().data_ptr<int64_t>(), B, NC, ld,
                        out.data_ptr<float>(), fopt_mut(acc), (float)weight, accumulate,
-                       rows.data_ptr<float>(), lse.data_ptr<float>(), cur_stream(), eps);
+                       rows.data_ptr<float>(), lse.data_ptr<float>(), cur_stream(), eps,
+                       mx.labels2, mx.lam);
   return lse;
 }
 
 Tensor ce_bwd(Tensor logits, Tensor labels, Tensor lse, Tensor grad_out, double weight,
-              double smoothing) {
+              double smoothing, c10::optional<Tensor> labels2, c10::optional<Tensor> lam) {
   const int ld = logits_ld(logits);
   const float eps = check_smoothing(smoothing);
+  const MixLabels mx = check_mix_labels(logits, labels2, lam);
   const int B = logits.size(0), NC = logits.size(1);
   const c10::OptionalDeviceGuard g(device_of(logits));
   Tensor d = torch::empty({B, ld}, logits.options());
   mpa::ce_bwd(bp(logits), labels.contiguous().data_ptr<int64_t>(), fopt(lse), fopt(grad_out), B,
-              NC, ld, bpm(d), cur_stream(), (float)weight, eps);
+              NC, ld, bpm(d), cur_stream(), (float)weight, eps, mx.labels2, mx.lam);
   return ld == NC ? d : d.narrow(1, 0, NC);
 }
 
@@ -1623,7 +1658,8 @@ void step_inc(Tensor step) {
 // pad: (top, bottom, left, right) zero border of the output canvas (empty = none)
 Tensor preprocess(Tensor img, int64_t OH, int64_t OW, std::vector<double> mean,
                   std::vector<double> stdv, int64_t mode, int64_t cpad, std::vector<int64_t> pad,
-                  c10::optional<Tensor> ext, c10::optional<Tensor> box) {
+                  c10::optional<Tensor> ext, c10::optional<Tensor> box,
+                  c10::optional<Tensor> mix, c10::optional<Tensor> lam) {
   CHECK_CUDA(img);
   CHECK_CONTIG(img);
   TORCH_CHECK(img.scalar_type() == torch::kUInt8 && img.dim() == 4 && img.size(3) == 3,
@@ -1664,8 +1700,29 @@ Tensor preprocess(Tensor img, int64_t OH, int64_t OW, std::vector<double> mean,
     TORCH_CHECK(box->device() == img.device(), "preprocess: box on another device");
     boxp = box->data_ptr<int>();
   }
+  const int* mixp = nullptr;
+  const float* lamp = nullptr;
+  const bool has_mix = mix && mix->defined(), has_lam = lam && lam->defined();
+  TORCH_CHECK(has_mix == has_lam, "preprocess: mix and lam go together");
+  if (has_mix) {
+    // Mixup / CutMix rows (partner, y0, x0, h, w) and weights; their values were checked by
+    // the caller (ops/functional.py) on its host copy, like the boxes
+    TORCH_CHECK(mode == 0, "preprocess: mixing with mode 0 only");
+    TORCH_CHECK(boxp, "preprocess: a mixed launch takes boxes (full-extent ones without a crop)");
+    TORCH_CHECK(mix->scalar_type() == torch::kInt32 && mix->dim() == 2 && mix->size(0) == B &&
+                    mix->size(1) == 5,
+                "preprocess: mix must be int32 [B,5]");
+    TORCH_CHECK(lam->scalar_type() == torch::kFloat32 && lam->dim() == 1 && lam->size(0) == B,
+                "preprocess: lam must be float32 [B]");
+    TORCH_CHECK(mix->device() == img.device() && lam->device() == img.device(),
+                "preprocess: mix / lam on another device");
+    TORCH_CHECK(mix->is_contiguous() && lam->is_contiguous(),
+                "preprocess: mix / lam must be contiguous");
+    mixp = mix->data_ptr<int>();
+    lamp = lam->data_ptr<float>();
+  }
   mpa::preprocess(img.data_ptr<uint8_t>(), B, H, W, OH, OW, n, mode, cpad, pd, bpm(out),
-                  cur_stream(), extp, boxp);
+                  cur_stream(), extp, boxp, mixp, lamp);
   return out;
 }
 
@@ -1997,12 +2054,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("linear_dgrad", &linear_dgrad, py::arg("dy"), py::arg("w"), py::arg("wt") = py::none());
   m.def("linear_wgrad", &linear_wgrad, py::arg("dy"), py::arg("x"), py::arg("dw"),
         py::arg("overwrite") = false);
-  m.def("ce_fwd", &ce_fwd, py::arg("logits"), py::arg("labels"), py::arg("smoothing") = 0.0);
+  m.def("ce_fwd", &ce_fwd, py::arg("logits"), py::arg("labels"), py::arg("smoothing") = 0.0,
+        py::arg("labels2") = py::none(), py::arg("lam") = py::none());
   m.def("ce_bwd", &ce_bwd, py::arg("logits"), py::arg("labels"), py::arg("lse"),
-        py::arg("grad_out"), py::arg("weight") = 1.0, py::arg("smoothing") = 0.0);
+        py::arg("grad_out"), py::arg("weight") = 1.0, py::arg("smoothing") = 0.0,
+        py::arg("labels2") = py::none(), py::arg("lam") = py::none());
   m.def("ce_fwd_weighted", &ce_fwd_weighted, py::arg("logits"), py::arg("labels"),
         py::arg("out"), py::arg("acc"), py::arg("weight"), py::arg("accumulate"),
-        py::arg("smoothing") = 0.0);
+        py::arg("smoothing") = 0.0, py::arg("labels2") = py::none(), py::arg("lam") = py::none());
   m.def("argmax_correct", &argmax_correct);
   m.def("topk_correct", &topk_correct, py::arg("logits"), py::arg("labels"), py::arg("k"),
         py::arg("count"));
@@ -2038,7 +2097,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("preprocess", &preprocess, py::arg("img"), py::arg("OH"), py::arg("OW"), py::arg("mean"),
         py::arg("std"), py::arg("mode"), py::arg("cpad"),
         py::arg("pad") = std::vector<int64_t>{}, py::arg("ext") = py::none(),
-        py::arg("box") = py::none());
+        py::arg("box") = py::none(), py::arg("mix") = py::none(), py::arg("lam") = py::none());
   m.def("dropout_fwd", &dropout_fwd, py::arg("x"), py::arg("p"), py::arg("seed"),
         py::arg("offset"), py::arg("counter") = py::none());
   m.def("dropout_bwd", &dropout_bwd);

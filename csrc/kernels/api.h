@@ -370,18 +370,24 @@ void split_channels(const bf16_raw* dy, const int* chans, int nseg, int pixels, 
 // loss.hip
 // logits rows have stride ld >= NC (padded heads); ce_bwd writes dlogits with stride ld and
 // zeros in columns NC..ld-1.  smoothing: torch's label_smoothing in [0, 1]; 0 runs the plain
-// kernels.
+// kernels.  labels2 + lam (optional device arrays [B], both or neither): row r's target is
+// lam[r] * onehot(labels[r]) + (1 - lam[r]) * onehot(labels2[r]) before smoothing (Mixup /
+// CutMix); null runs the one-label kernels.
 void ce_fwd_rows(const bf16_raw* logits, const int64_t* labels, int B, int NC, int ld, float* row_loss,
-                 float* lse, hipStream_t s, float smoothing = 0.f);
+                 float* lse, hipStream_t s, float smoothing = 0.f,
+                 const int64_t* labels2 = nullptr, const float* lam = nullptr);
 // loss: [1 + B] floats (mean at [0], per-row terms after it; fixed-order sum)
 void ce_fwd(const bf16_raw* logits, const int64_t* labels, int B, int NC, int ld, float* loss,
-            float* lse, hipStream_t s, float smoothing = 0.f);
+            float* lse, hipStream_t s, float smoothing = 0.f, const int64_t* labels2 = nullptr,
+            const float* lam = nullptr);
 void ce_bwd(const bf16_raw* logits, const int64_t* labels, const float* lse,
             const float* grad_out, int B, int NC, int ld, bf16_raw* dlogits, hipStream_t s,
-            float weight = 1.f, float smoothing = 0.f);
+            float weight = 1.f, float smoothing = 0.f, const int64_t* labels2 = nullptr,
+            const float* lam = nullptr);
 void ce_fwd_weighted(const bf16_raw* logits, const int64_t* labels, int B, int NC, int ld,
                      float* out, float* acc, float weight, bool accumulate, float* rows,
-                     float* lse, hipStream_t s, float smoothing = 0.f);
+                     float* lse, hipStream_t s, float smoothing = 0.f,
+                     const int64_t* labels2 = nullptr, const float* lam = nullptr);
 // fp32 t[0:n) = 0 (n % 4 == 0, 16-B aligned); step[0] += 1
 void zero_f32(float* t, int64_t n, hipStream_t s);
 void add_f32(float* dst, const float* src, int64_t n, hipStream_t s);  // dst += src
@@ -493,9 +499,14 @@ void preprocess_set_copy(int on);  // identity-size fast path on/off (tests, A/B
 // box (optional, mode 0 only): per-image crop boxes [B][5] = (y0, x0, h, w, flip) in source
 // pixels of image b's slot; image b is resized from its box (which must lie inside its
 // extent - the caller checks, the kernel does not) and mirrored along W when flip != 0
+// mix + lam (optional, mode 0 only, both or neither, and then box is required - full-extent
+// boxes when there is no crop): Mixup / CutMix.  mix [B][5] = (partner, y0, x0, h, w) - an
+// image of the same batch and a rectangle in output pixels (inside [0, OH] x [0, OW]; h or
+// w == 0: none) - and lam [B] in [0, 1]: the output is the partner's inside the rectangle
+// and bf16(lam * own + (1 - lam) * partner's) outside it (trusted like the boxes)
 void preprocess(const uint8_t* img, int B, int H, int W, int OH, int OW, Norm3 nrm, int mode,
                 int cpad, OutPad pad, bf16_raw* out, hipStream_t s, const int* ext = nullptr,
-                const int* box = nullptr);
+                const int* box = nullptr, const int* mix = nullptr, const float* lam = nullptr);
 // PIL-exact bicubic (eval transform): per-image extents ext [B][2] (h, w) inside the
 // [Hp][Wp] pitch (nullptr: all full), per-image table selectors sel [B][2]; tmp holds
 // B * Hp * OW RGBx words

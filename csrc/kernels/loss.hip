@@ -20,6 +20,15 @@
 // sits under "if constexpr (SMOOTH)", and eps == 0 launches the SMOOTH = false
 // instantiations: the plain loss runs the code it ran before smoothing existed.
 //
+// MIX (Mixup / CutMix, two labels per row): the target is lam * onehot(y) + (1 - lam) *
+// onehot(y2) before smoothing, with lam read per row from device memory (a captured graph
+// replays with new values).  The forward looks up a second logit, row loss = lse - (1-eps) *
+// (lam * x[y] + (1-lam) * x[y2]) - (eps/NC) * sum_c x[c]; the backward subtracts (1-eps) *
+// (lam * [c == y] + (1-lam) * [c == y2]), the two weights added first, so y == y2 and a
+// swap of (y, lam) with (y2, 1-lam) come out right.  Everything it adds sits under "if
+// constexpr (MIX)" - the kernel arguments too (CeMix) - and null labels2 launches the
+// MIX = false instantiations: the one-label loss runs the code it ran before.
+//
 // Top-k accuracy (topk_correct): no selection or sort - a row is correct iff fewer than k
 // columns outrank its label's logit, ties going to the lower index (argmax_kernel's rule).
 #include "common.h"
@@ -49,13 +58,33 @@ __device__ __forceinline__ void lse_merge(float& m, float& s, float m2, float s2
   m = mn;
 }
 
+// lam * a + (1 - lam) * b with every operation rounded on its own: exactly a at lam == 1
+// and b at lam == 0, and symmetric under (a, lam) <-> (b, 1 - lam) for dyadic lam
+__device__ __forceinline__ float ce_mix2(float lam, float a, float b) {
+#pragma clang fp contract(off)
+  const float om = 1.f - lam;
+  const float pa = lam * a;
+  const float pb = om * b;
+  return pa + pb;
+}
+
+// the MIX instantiations' extra kernel arguments (an empty argument otherwise)
+template <bool MIX>
+struct CeMix {};
+template <>
+struct CeMix<true> {
+  const int64_t* labels2;  // [B]
+  const float* lam;        // [B]
+};
+
 // Block-reduce the per-thread (m, s) - and, SMOOTH, the logit sum t - in a fixed order
 // (wave shuffle, then 4 LDS entries) and have thread 0 write the row's lse and loss term.
-template <bool SMOOTH>
+template <bool SMOOTH, bool MIX>
 __device__ __forceinline__ void ce_row_finish(float m, float s, float t, const bf16_t* x, int row,
                                               const int64_t* __restrict__ labels, int B, int NC,
                                               float* __restrict__ row_loss,
-                                              float* __restrict__ lse_out, float eps) {
+                                              float* __restrict__ lse_out, float eps,
+                                              const CeMix<MIX>& mx) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) {
     const float m2 = __shfl_xor(m, o, 64), s2 = __shfl_xor(s, o, 64);
@@ -75,7 +104,18 @@ __device__ __forceinline__ void ce_row_finish(float m, float s, float t, const b
     const float lse = M + __logf(S);
     lse_out[row] = lse;
     const int64_t lab = labels[row];
-    if constexpr (SMOOTH) {
+    if constexpr (MIX) {  // both labels valid (the callers' contract)
+      const int64_t lab2 = mx.labels2[row];
+      const bool ok = lab >= 0 && lab < NC && lab2 >= 0 && lab2 < NC;
+      const float picked = ce_mix2(mx.lam[row], bf2f(x[ok ? lab : 0]), bf2f(x[ok ? lab2 : 0]));
+      if constexpr (SMOOTH) {
+        const float T = (st[0] + st[1]) + (st[2] + st[3]);
+        const float l = lse - (1.f - eps) * picked - (eps / (float)NC) * T;
+        row_loss[row] = ok ? l / (float)B : 0.f;
+      } else {
+        row_loss[row] = (lse - (ok ? picked : lse)) / (float)B;
+      }
+    } else if constexpr (SMOOTH) {
       const float T = (st[0] + st[1]) + (st[2] + st[3]);
       const float l = lse - (1.f - eps) * bf2f(x[lab >= 0 && lab < NC ? lab : 0]) -
                       (eps / (float)NC) * T;
@@ -87,11 +127,12 @@ __device__ __forceinline__ void ce_row_finish(float m, float s, float t, const b
   }
 }
 
-template <int V, bool SMOOTH = false>
+template <int V, bool SMOOTH = false, bool MIX = false>
 __global__ __launch_bounds__(256) void ce_fwd_kernel(const bf16_t* __restrict__ logits,
                                                       const int64_t* __restrict__ labels, int B,
                                                       int NC, int ld, float* __restrict__ row_loss,
-                                                      float* __restrict__ lse_out, float eps) {
+                                                      float* __restrict__ lse_out, float eps,
+                                                      CeMix<MIX> mx) {
   const int row = blockIdx.x;
   const bf16_t* x = logits + (size_t)row * ld;
   float m = -INFINITY, s = 0.f, t = 0.f;
@@ -113,20 +154,20 @@ __global__ __launch_bounds__(256) void ce_fwd_kernel(const bf16_t* __restrict__ 
       for (int j = 0; j < V; ++j) t += f[j];
     }
   }
-  ce_row_finish<SMOOTH>(m, s, t, x, row, labels, B, NC, row_loss, lse_out, eps);
+  ce_row_finish<SMOOTH, MIX>(m, s, t, x, row, labels, B, NC, row_loss, lse_out, eps, mx);
 }
 
 // Padded rows (ld % 8 == 0, 16-B aligned; the 64,500-class head has ld = 64,512): 16-B
 // loads over the whole padded row with columns >= NC masked to -inf, U loads issued before
 // any is consumed.  The unpadded kernel above walked 64,500 columns in 8-B loads, one load
 // per online-LSE step, and streamed ~2.2 TB/s (30 us per 66 MB of logits).
-template <int U, bool SMOOTH = false>
+template <int U, bool SMOOTH = false, bool MIX = false>
 __global__ __launch_bounds__(256) void ce_fwd_padded_kernel(const bf16_t* __restrict__ logits,
                                                              const int64_t* __restrict__ labels,
                                                              int B, int NC, int ld,
                                                              float* __restrict__ row_loss,
                                                              float* __restrict__ lse_out,
-                                                             float eps) {
+                                                             float eps, CeMix<MIX> mx) {
   const int row = blockIdx.x;
   const bf16_t* x = logits + (size_t)row * ld;
   float m = -INFINITY, s = 0.f, t = 0.f;
@@ -159,17 +200,19 @@ __global__ __launch_bounds__(256) void ce_fwd_padded_kernel(const bf16_t* __rest
       s = acc;
     }
   }
-  ce_row_finish<SMOOTH>(m, s, t, x, row, labels, B, NC, row_loss, lse_out, eps);
+  ce_row_finish<SMOOTH, MIX>(m, s, t, x, row, labels, B, NC, row_loss, lse_out, eps, mx);
 }
 
 // SMOOTH: onw = 1 - eps is the label's weight, unif = eps / NC every class's share.
-template <int V, bool SMOOTH = false>
+// MIX: column c loses onw * (lam * [c == y] + (1 - lam) * [c == y2]).
+template <int V, bool SMOOTH = false, bool MIX = false>
 __global__ __launch_bounds__(256) void ce_bwd_kernel(const bf16_t* __restrict__ logits,
                                                       const int64_t* __restrict__ labels,
                                                       const float* __restrict__ lse,
                                                       const float* __restrict__ grad_out, int B,
                                                       int NC, int ld, bf16_t* __restrict__ dlogits,
-                                                      float weight, float onw, float unif) {
+                                                      float weight, float onw, float unif,
+                                                      CeMix<MIX> mx) {
   const float scale = grad_out[0] * weight / (float)B;
   const int nv = ld / V;  // whole padded row: columns >= NC get zero gradient
   const int64_t total = (int64_t)B * nv;
@@ -179,13 +222,24 @@ __global__ __launch_bounds__(256) void ce_bwd_kernel(const bf16_t* __restrict__ 
     const int c0 = (int)(t - (int64_t)row * nv) * V;
     const float l = lse[row];
     const int64_t lab = labels[row];
+    int64_t lab2 = 0;
+    float lam = 1.f;
+    if constexpr (MIX) lab2 = mx.labels2[row], lam = mx.lam[row];
     float f[V];
     const size_t off = (size_t)row * ld + c0;
     load_v<V>(logits + off, f);
 #pragma unroll
     for (int j = 0; j < V; ++j) {
       float p = __expf(f[j] - l);
-      if constexpr (SMOOTH) {
+      if constexpr (MIX) {
+        if constexpr (SMOOTH) p -= unif;
+        if (c0 + j == lab || c0 + j == lab2) {  // the two weights first: their sum is exact
+                                                // for lam = 1, 0 and dyadic values
+          const float w = (c0 + j == lab ? lam : 0.f) + (c0 + j == lab2 ? 1.f - lam : 0.f);
+          if constexpr (SMOOTH) p -= onw * w;
+          else p -= w;
+        }
+      } else if constexpr (SMOOTH) {
         p -= unif;
         if (c0 + j == lab) p -= onw;
       } else {
@@ -314,9 +368,10 @@ __global__ __launch_bounds__(256) void ce_loss_sum_kernel(const float* __restric
 
 // loss: [1 + B] floats - the mean loss at [0], the per-row terms after it
 void ce_fwd(const bf16_raw* logits, const int64_t* labels, int B, int NC, int ld, float* loss,
-            float* lse, hipStream_t s, float smoothing) {
+            float* lse, hipStream_t s, float smoothing, const int64_t* labels2,
+            const float* lam) {
   float* rows = loss + 1;
-  ce_fwd_rows(logits, labels, B, NC, ld, rows, lse, s, smoothing);
+  ce_fwd_rows(logits, labels, B, NC, ld, rows, lse, s, smoothing, labels2, lam);
   hipLaunchKernelGGL(ce_loss_sum_kernel, dim3(1), dim3(256), 0, s, rows, B, loss,
                      0, 1.f, (float*)nullptr);
 }
@@ -325,8 +380,9 @@ void ce_fwd(const bf16_raw* logits, const int64_t* labels, int B, int NC, int ld
 // scratch.  Several heads (Inception's main + 0.4 * aux) sum into one loss this way.
 void ce_fwd_weighted(const bf16_raw* logits, const int64_t* labels, int B, int NC, int ld,
                      float* out, float* acc, float weight, bool accumulate, float* rows,
-                     float* lse, hipStream_t s, float smoothing) {
-  ce_fwd_rows(logits, labels, B, NC, ld, rows, lse, s, smoothing);
+                     float* lse, hipStream_t s, float smoothing, const int64_t* labels2,
+                     const float* lam) {
+  ce_fwd_rows(logits, labels, B, NC, ld, rows, lse, s, smoothing, labels2, lam);
   hipLaunchKernelGGL(ce_loss_sum_kernel, dim3(1), dim3(256), 0, s, rows, B, out,
                      accumulate ? 1 : 0, weight, acc);
 }
@@ -336,24 +392,55 @@ static void ce_fwd_rows_t(const bf16_raw* logits, const int64_t* labels, int B, 
                           float* loss, float* lse, hipStream_t s, float eps) {
   if (ld % 8 == 0 && ld >= NC && reinterpret_cast<uintptr_t>(logits) % 16 == 0) {
     hipLaunchKernelGGL((ce_fwd_padded_kernel<4, SMOOTH>), dim3(B), dim3(256), 0, s, logits,
-                       labels, B, NC, ld, loss, lse, eps);
+                       labels, B, NC, ld, loss, lse, eps, CeMix<false>{});
     return;
   }
   const int g = NC % 8 == 0 && ld % 8 == 0 ? 8 : (NC % 4 == 0 && ld % 4 == 0 ? 4 : 1);
   if (g == 8)
     hipLaunchKernelGGL((ce_fwd_kernel<8, SMOOTH>), dim3(B), dim3(256), 0, s, logits, labels, B,
-                       NC, ld, loss, lse, eps);
+                       NC, ld, loss, lse, eps, CeMix<false>{});
   else if (g == 4)
     hipLaunchKernelGGL((ce_fwd_kernel<4, SMOOTH>), dim3(B), dim3(256), 0, s, logits, labels, B,
-                       NC, ld, loss, lse, eps);
+                       NC, ld, loss, lse, eps, CeMix<false>{});
   else
     hipLaunchKernelGGL((ce_fwd_kernel<1, SMOOTH>), dim3(B), dim3(256), 0, s, logits, labels, B,
-                       NC, ld, loss, lse, eps);
+                       NC, ld, loss, lse, eps, CeMix<false>{});
 }
 
-// smoothing == 0 launches the SMOOTH = false instantiations (the plain loss, unchanged)
+// the same choice of kernel with two labels per row
+template <bool SMOOTH>
+static void ce_fwd_rows_mix_t(const bf16_raw* logits, const int64_t* labels, int B, int NC,
+                              int ld, float* loss, float* lse, hipStream_t s, float eps,
+                              const int64_t* labels2, const float* lam) {
+  if (ld % 8 == 0 && ld >= NC && reinterpret_cast<uintptr_t>(logits) % 16 == 0) {
+    hipLaunchKernelGGL((ce_fwd_padded_kernel<4, SMOOTH, true>), dim3(B), dim3(256), 0, s, logits,
+                       labels, B, NC, ld, loss, lse, eps, CeMix<true>{labels2, lam});
+    return;
+  }
+  const int g = NC % 8 == 0 && ld % 8 == 0 ? 8 : (NC % 4 == 0 && ld % 4 == 0 ? 4 : 1);
+  if (g == 8)
+    hipLaunchKernelGGL((ce_fwd_kernel<8, SMOOTH, true>), dim3(B), dim3(256), 0, s, logits, labels,
+                       B, NC, ld, loss, lse, eps, CeMix<true>{labels2, lam});
+  else if (g == 4)
+    hipLaunchKernelGGL((ce_fwd_kernel<4, SMOOTH, true>), dim3(B), dim3(256), 0, s, logits, labels,
+                       B, NC, ld, loss, lse, eps, CeMix<true>{labels2, lam});
+  else
+    hipLaunchKernelGGL((ce_fwd_kernel<1, SMOOTH, true>), dim3(B), dim3(256), 0, s, logits, labels,
+                       B, NC, ld, loss, lse, eps, CeMix<true>{labels2, lam});
+}
+
+// smoothing == 0 launches the SMOOTH = false instantiations, null labels2 the one-label
+// ones (the plain loss, unchanged)
 void ce_fwd_rows(const bf16_raw* logits, const int64_t* labels, int B, int NC, int ld, float* loss,
-                 float* lse, hipStream_t s, float smoothing) {
+                 float* lse, hipStream_t s, float smoothing, const int64_t* labels2,
+                 const float* lam) {
+  if (labels2) {
+    if (smoothing != 0.f)
+      ce_fwd_rows_mix_t<true>(logits, labels, B, NC, ld, loss, lse, s, smoothing, labels2, lam);
+    else
+      ce_fwd_rows_mix_t<false>(logits, labels, B, NC, ld, loss, lse, s, 0.f, labels2, lam);
+    return;
+  }
   if (smoothing != 0.f) ce_fwd_rows_t<true>(logits, labels, B, NC, ld, loss, lse, s, smoothing);
   else ce_fwd_rows_t<false>(logits, labels, B, NC, ld, loss, lse, s, 0.f);
 }
@@ -361,29 +448,38 @@ void ce_fwd_rows(const bf16_raw* logits, const int64_t* labels, int B, int NC, i
 template <bool SMOOTH>
 static void ce_bwd_t(const bf16_raw* logits, const int64_t* labels, const float* lse,
                      const float* grad_out, int B, int NC, int ld, bf16_raw* dlogits,
-                     hipStream_t s, float weight, float eps) {
+                     hipStream_t s, float weight, float eps, const int64_t* labels2,
+                     const float* lam) {
   const int V = (ld % 8 == 0) ? 8 : (ld % 4 == 0 ? 4 : 1);
   const int64_t total = (int64_t)B * (ld / V);
   const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>((total + 255) / 256, 8192));
   const float onw = 1.f - eps, unif = eps / (float)NC;
-  if (V == 8)
-    hipLaunchKernelGGL((ce_bwd_kernel<8, SMOOTH>), dim3(blocks), dim3(256), 0, s, logits, labels,
-                       lse, grad_out, B, NC, ld, dlogits, weight, onw, unif);
-  else if (V == 4)
-    hipLaunchKernelGGL((ce_bwd_kernel<4, SMOOTH>), dim3(blocks), dim3(256), 0, s, logits, labels,
-                       lse, grad_out, B, NC, ld, dlogits, weight, onw, unif);
-  else
-    hipLaunchKernelGGL((ce_bwd_kernel<1, SMOOTH>), dim3(blocks), dim3(256), 0, s, logits, labels,
-                       lse, grad_out, B, NC, ld, dlogits, weight, onw, unif);
+#define CE_BWD(VV)                                                                               \
+  do {                                                                                           \
+    if (labels2)                                                                                 \
+      hipLaunchKernelGGL((ce_bwd_kernel<VV, SMOOTH, true>), dim3(blocks), dim3(256), 0, s,       \
+                         logits, labels, lse, grad_out, B, NC, ld, dlogits, weight, onw, unif,   \
+                         CeMix<true>{labels2, lam});                                             \
+    else                                                                                         \
+      hipLaunchKernelGGL((ce_bwd_kernel<VV, SMOOTH>), dim3(blocks), dim3(256), 0, s, logits,     \
+                         labels, lse, grad_out, B, NC, ld, dlogits, weight, onw, unif,           \
+                         CeMix<false>{});                                                        \
+  } while (0)
+  if (V == 8) CE_BWD(8);
+  else if (V == 4) CE_BWD(4);
+  else CE_BWD(1);
+#undef CE_BWD
 }
 
 void ce_bwd(const bf16_raw* logits, const int64_t* labels, const float* lse,
             const float* grad_out, int B, int NC, int ld, bf16_raw* dlogits, hipStream_t s,
-            float weight, float smoothing) {
+            float weight, float smoothing, const int64_t* labels2, const float* lam) {
   if (smoothing != 0.f)
-    ce_bwd_t<true>(logits, labels, lse, grad_out, B, NC, ld, dlogits, s, weight, smoothing);
+    ce_bwd_t<true>(logits, labels, lse, grad_out, B, NC, ld, dlogits, s, weight, smoothing,
+                   labels2, lam);
   else
-    ce_bwd_t<false>(logits, labels, lse, grad_out, B, NC, ld, dlogits, s, weight, 0.f);
+    ce_bwd_t<false>(logits, labels, lse, grad_out, B, NC, ld, dlogits, s, weight, 0.f, labels2,
+                    lam);
 }
 
 void argmax_correct(const bf16_raw* logits, const int64_t* labels, int B, int NC, int ld,

@@ -201,6 +201,206 @@ __global__ __launch_bounds__(256) void preprocess_bilinear_kernel(
   }
 }
 
+// Mixup / CutMix (preprocess_bilinear_mix_kernel; always with crop boxes, full-extent ones
+// when nothing is cropped): image b also has a partner image of the same batch, a rectangle
+// in output pixels and a weight - mix[b] = (partner, y0, x0, h, w), lam[b].  With P the
+// bf16 result of the same launch without mixing, the output is P[partner] inside the
+// rectangle and bf16(lam * P[b] + (1 - lam) * P[partner]) outside it (P[b] / P[partner]
+// themselves at lam == 1 / 0).  The block that owns row group r of image b stages the tap
+// rows of image b and - when the row group reads the partner at all (lam != 1, or the
+// rectangle crosses it) - of the partner, each with its own crop box and flip, computes
+// both pixels as the BOX kernel would have stored them (same arithmetic, rounded to bf16),
+// blends in fp32 with individually rounded operations (pp_blend) and stores once.  LDS
+// holds two images' tap rows, so only slots up to PP_MIX_MAXW wide are staged and wider
+// ones read from global memory.  It is a kernel of its own, not a flag of the one above:
+// the plain and boxed instantiations keep their arguments and compile to the code they had.
+constexpr int PP_MIX_MAXW = PP_MAXW / 2;
+
+// lam * a + (1 - lam) * b: one subtraction, two multiplications, one addition, each
+// rounded to fp32 on its own (nothing contracted into an FMA), so the result is bitwise
+// the same expression of any other fp32 implementation
+__device__ __forceinline__ float pp_blend(float lam, float a, float b) {
+#pragma clang fp contract(off)
+  const float om = 1.f - lam;
+  const float pa = lam * a;
+  const float pb = om * b;
+  return pa + pb;
+}
+
+// one image's crop: its slot's first byte, the crop's size and origin, mirror, the bytes
+// between the VEC-aligned start of the staging loads and the crop's first byte, vectors
+// per staged row, source pixels per output pixel
+struct PpSrc {
+  const uint8_t* base;
+  int ih, iw, by0, bx0, flip, slack, per;
+  float sh, sw;
+};
+
+// STAGED, VEC, CPAD as above; box [B][5] as the BOX instantiations take it
+template <bool STAGED, int VEC, int CPAD>
+__global__ __launch_bounds__(256) void preprocess_bilinear_mix_kernel(
+    const uint8_t* __restrict__ img, int B, int H, int W, int OH, int OW,
+    Norm3 nrm, int cpad_rt, OutPad pd, bf16_t* __restrict__ out, const int* __restrict__ box,
+    const int* __restrict__ mix, const float* __restrict__ lamv) {
+  const int cpad = CPAD ? CPAD : cpad_rt;
+  extern __shared__ __attribute__((aligned(16))) uint8_t srow[];  // [2][PP_ROWS][2][rb]
+  const float* mean = nrm.mean;
+  const float* stdv = nrm.std;
+  const float i0 = 1.f / (255.f * stdv[0]), i1 = 1.f / (255.f * stdv[1]), i2 = 1.f / (255.f * stdv[2]);
+  const float o0 = mean[0] / stdv[0], o1 = mean[1] / stdv[1], o2 = mean[2] / stdv[2];
+  const int ohp = OH + pd.top + pd.bottom, owp = OW + pd.left + pd.right;
+  const int ngroups = (ohp + PP_ROWS - 1) / PP_ROWS;
+  const int rb = W * 3;
+  const int rbp = (rb + 15) & ~15;
+  constexpr int vec = VEC;
+  uint8_t* const srow1 = srow + PP_ROWS * 2 * rbp;  // the partner's staged rows
+  for (int item = blockIdx.x; item < B * ngroups; item += gridDim.x) {
+    const int b = item / ngroups;
+    const int row0 = (item - b * ngroups) * PP_ROWS;
+    const int nrows = min(PP_ROWS, ohp - row0);
+    auto source = [&](int bi) {
+      PpSrc g;
+      const int* bx = box + 5 * bi;
+      g.base = img + (size_t)bi * H * W * 3;
+      g.by0 = bx[0], g.bx0 = bx[1], g.ih = bx[2], g.iw = bx[3], g.flip = bx[4];
+      g.sh = (float)g.ih / OH, g.sw = (float)g.iw / OW;
+      g.slack = (g.bx0 * 3) & (vec - 1);
+      g.per = (g.slack + g.iw * 3 + vec - 1) / vec;
+      return g;
+    };
+    const int* mr = mix + 5 * b;
+    const PpSrc g0 = source(b), g1 = source(mr[0]);
+    // the rectangle [my0, my1) x [mx0, mx1) in output pixels (h or w == 0: none)
+    const bool rect = mr[3] > 0 && mr[4] > 0;
+    const int my0 = mr[1], mx0 = mr[2], my1 = rect ? my0 + mr[3] : my0, mx1 = rect ? mx0 + mr[4] : mx0;
+    const float lam = lamv[b];
+    // does any pixel of this row group read the partner (block-uniform)
+    const int oya = row0 - pd.top, oyb = oya + nrows;  // its image rows [oya, oyb)
+    const bool need1 = lam != 1.f || (rect && my0 < oyb && my1 > oya);
+    auto tap_rows = [&](const PpSrc& g, int r, int& y0, int& y1, float& ly) {
+#pragma clang fp contract(off)
+      const int oy = row0 + r - pd.top;
+      const float sy = fmaxf(__builtin_fmaf(oy + 0.5f, g.sh, -0.5f), 0.f);
+      y0 = min((int)sy, g.ih - 1);
+      y1 = min(y0 + 1, g.ih - 1);
+      ly = sy - y0;
+    };
+    // phase 1 of one image, as in the kernel above: every (row, tap) source row's crop span
+    auto stage = [&](const PpSrc& g, uint8_t* dst) {
+      const int total = nrows * 2 * g.per;
+      for (int j0 = threadIdx.x; j0 < total; j0 += 4 * blockDim.x) {
+        uint4 v[4];
+        int dsto[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          const int i = j0 + k * blockDim.x;
+          dsto[k] = -1;
+          if (i >= total) continue;
+          const int rt = i / g.per, e = i - rt * g.per;  // rt = 2 * row + tap
+          const int oy = row0 + (rt >> 1) - pd.top;
+          if ((unsigned)oy >= (unsigned)OH) continue;  // border row: nothing to stage
+          int y0, y1;
+          float ly;
+          tap_rows(g, rt >> 1, y0, y1, ly);
+          const uint8_t* src = g.base + (size_t)(g.by0 + ((rt & 1) ? y1 : y0)) * rb +
+                               (g.bx0 * 3 - g.slack);
+          dsto[k] = rt * rbp + e * vec;
+          if constexpr (vec == 16) v[k] = ((const uint4*)src)[e];
+          else if constexpr (vec == 4) v[k].x = ((const uint32_t*)src)[e];
+          else v[k].x = src[e];
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          if (dsto[k] < 0) continue;
+          if constexpr (vec == 16) *(uint4*)(dst + dsto[k]) = v[k];
+          else if constexpr (vec == 4) *(uint32_t*)(dst + dsto[k]) = v[k].x;
+          else dst[dsto[k]] = (uint8_t)v[k].x;
+        }
+      }
+    };
+    if constexpr (STAGED) {
+      __syncthreads();  // the previous item's readers are done with srow
+      stage(g0, srow);
+      if (need1) stage(g1, srow1);
+      __syncthreads();
+    }
+    // the two tap rows (first crop byte) of canvas row r: staged, or in global memory
+    auto taps = [&](const PpSrc& g, const uint8_t* lds, int r, const uint8_t*& t0,
+                    const uint8_t*& t1, float& ly) {
+      int y0, y1;
+      tap_rows(g, r, y0, y1, ly);
+      if constexpr (STAGED) {
+        t0 = lds + (2 * r) * rbp + g.slack;
+        t1 = lds + (2 * r + 1) * rbp + g.slack;
+      } else {
+        t0 = g.base + (size_t)(g.by0 + y0) * rb + g.bx0 * 3;
+        t1 = g.base + (size_t)(g.by0 + y1) * rb + g.bx0 * 3;
+      }
+    };
+    // Output column ox as the BOX kernel stores it, rounded to bf16.  That kernel's
+    // expressions are contracted by the compiler (-ffp-contract=fast), and a second copy of
+    // them need not be contracted the same way, so the operations it compiles to are spelled
+    // out here: fma(s, o + 0.5, -0.5) for the source coordinates, fma(1 - l, a, l * b) for
+    // each of the three interpolations, fma(c, 1 / (255 std), -mean / std).  One exception:
+    // the CPAD = 0 instantiations above compute channels 0 and 1 with packed operations,
+    // and there channel 0's two horizontal interpolations fuse the other product, fma(l, b,
+    // (1 - l) * a).  The tests hold the mixed launch bitwise to the un-mixed one in every
+    // layout and staging width, which is what keeps the two in step.
+    auto pixel = [&](const PpSrc& g, const uint8_t* t0, const uint8_t* t1, float ly, int ox,
+                     float* p) {
+#pragma clang fp contract(off)
+      const int rx = g.flip ? OW - 1 - ox : ox;  // the column in the unflipped resize
+      const float sx = fmaxf(__builtin_fmaf(rx + 0.5f, g.sw, -0.5f), 0.f);
+      const int x0 = min((int)sx, g.iw - 1), x1 = min(x0 + 1, g.iw - 1);
+      const float lx = sx - x0, wx = 1.f - lx, wy = 1.f - ly;
+      float c[3];
+#pragma unroll
+      for (int ch = 0; ch < 3; ++ch) {
+        const float v00 = t0[x0 * 3 + ch], v01 = t0[x1 * 3 + ch];
+        const float v10 = t1[x0 * 3 + ch], v11 = t1[x1 * 3 + ch];
+        const bool other = CPAD == 0 && ch == 0;
+        const float top = other ? __builtin_fmaf(lx, v01, wx * v00) : __builtin_fmaf(wx, v00, lx * v01);
+        const float bot = other ? __builtin_fmaf(lx, v11, wx * v10) : __builtin_fmaf(wx, v10, lx * v11);
+        c[ch] = __builtin_fmaf(wy, top, ly * bot);
+      }
+      p[0] = bf2f(f2bf(__builtin_fmaf(c[0], i0, -o0)));
+      p[1] = bf2f(f2bf(__builtin_fmaf(c[1], i1, -o1)));
+      p[2] = bf2f(f2bf(__builtin_fmaf(c[2], i2, -o2)));
+    };
+    for (int r = 0; r < nrows; ++r) {  // phase 2
+      const int oy = row0 + r - pd.top;
+      bf16_t* orow = out + ((size_t)b * ohp + row0 + r) * owp * cpad;
+      const bool brow = (unsigned)oy >= (unsigned)OH;
+      const uint8_t *t0, *t1, *u0 = nullptr, *u1 = nullptr;
+      float ly, lyu = 0.f;
+      taps(g0, srow, r, t0, t1, ly);
+      if (need1) taps(g1, srow1, r, u0, u1, lyu);
+      const bool rrow = oy >= my0 && oy < my1;  // the rectangle crosses this row
+      for (int px = threadIdx.x; px < owp; px += blockDim.x) {
+        const int ox = px - pd.left;
+        bf16_t* o = orow + (size_t)px * cpad;
+        if (brow || (unsigned)ox >= (unsigned)OW) {
+          store_px(o, 0.f, 0.f, 0.f, cpad);
+          continue;
+        }
+        float p[3];
+        pixel(g0, t0, t1, ly, ox, p);
+        if (need1) {
+          float q[3];
+          pixel(g1, u0, u1, lyu, ox, q);
+          const bool inside = rrow && ox >= mx0 && ox < mx1;
+#pragma unroll
+          for (int ch = 0; ch < 3; ++ch)
+            p[ch] = (inside || lam == 0.f) ? q[ch]
+                    : lam == 1.f           ? p[ch]
+                                           : pp_blend(lam, p[ch], q[ch]);
+        }
+        store_px(o, p[0], p[1], p[2], cpad);  // (rounding a bf16 value again changes nothing)
+      }
+    }
+  }
+}
+
 // Identity resize (OH == H, OW == W: bilinear weights are exactly 0 / 1, so the result is
 // bitwise the bilinear kernel's) into the 4-channel pixel-pair stem canvas - the training
 // benchmark's synthetic images arrive at the output size.  A pure stream (u8 in, 8-B bf16
@@ -465,10 +665,10 @@ void preprocess_set_copy(int on) { g_pre_copy = on; }
 
 void preprocess(const uint8_t* img, int B, int H, int W, int OH, int OW, Norm3 nrm, int mode,
                 int cpad, OutPad pd, bf16_raw* out, hipStream_t s, const int* ext,
-                const int* box) {
+                const int* box, const int* mix, const float* lam) {
   if (B <= 0) return;  // bicubic: gridDim.y = images (<= 65535)
   const int ohp = OH + pd.top + pd.bottom, owp = OW + pd.left + pd.right;
-  if (mode == 0 && !ext && !box && g_pre_copy && H == OH && W == OW && cpad == 4 && W % 4 == 0 &&
+  if (mode == 0 && !ext && !box && !mix && g_pre_copy && H == OH && W == OW && cpad == 4 && W % 4 == 0 &&
       reinterpret_cast<uintptr_t>(img) % 4 == 0 && (int64_t)B * ohp < (1ll << 30)) {
     hipLaunchKernelGGL(preprocess_copy4_kernel, dim3((B * ohp + 3) / 4), dim3(256), 0, s, img, B,
                        H, W, nrm, pd, out);
@@ -481,6 +681,27 @@ void preprocess(const uint8_t* img, int B, int H, int W, int OH, int OW, Norm3 n
     const int rb = W * 3;
     const uintptr_t ia = (uintptr_t)img;
     const int vec = (rb % 16 == 0 && ia % 16 == 0) ? 16 : (rb % 4 == 0 && ia % 4 == 0) ? 4 : 1;
+    if (mix) {
+      // a mixed launch (box, mix and lam all set; the binding checks): two images' tap rows
+      // share the LDS, so only slots up to PP_MIX_MAXW wide are staged
+      const size_t lds2 = 2 * lds;
+#define PP_MIX_CP(ST, V, CP, L)                                                                 \
+  hipLaunchKernelGGL((preprocess_bilinear_mix_kernel<ST, V, CP>), grid, dim3(256), L, s, img,   \
+                     B, H, W, OH, OW, nrm, cpad, pd, out, box, mix, lam)
+#define PP_MIX(ST, V, L)                       \
+  do {                                         \
+    if (cpad == 4) PP_MIX_CP(ST, V, 4, L);     \
+    else if (cpad == 8) PP_MIX_CP(ST, V, 8, L); \
+    else PP_MIX_CP(ST, V, 0, L);               \
+  } while (0)
+      if (W > PP_MIX_MAXW) PP_MIX(false, 1, 0);
+      else if (vec == 16) PP_MIX(true, 16, lds2);
+      else if (vec == 4) PP_MIX(true, 4, lds2);
+      else PP_MIX(true, 1, lds2);
+#undef PP_MIX
+#undef PP_MIX_CP
+      return;
+    }
     // a box replaces the extent (it lies inside it): the BOX kernels take it in ext's place
 #define PP_LAUNCH(ST, V, CP, L)                                                                 \
   do {                                                                                          \

@@ -78,6 +78,12 @@ class Config:
     augment: str = "none"                  # none | flip | rrc (random-resized crop + flip)
     aug_scale_min: float = 0.08            # rrc: smallest crop, as a fraction of the image area
     label_smoothing: float = 0.0           # training-loss label smoothing in [0, 1] (0 = off)
+    # sample mixing of the training loader (data/augment.py::sample_mix): images blended in
+    # the preprocess launch, labels in the fused cross-entropy; off when both alphas are 0
+    mixup_alpha: float = 0.0               # Mixup: lam ~ Beta(alpha, alpha)
+    cutmix_alpha: float = 0.0              # CutMix: the pasted rectangle's area from Beta(alpha, alpha)
+    mix_prob: float = 1.0                  # probability that a sample is mixed at all
+    mix_switch_prob: float = 0.5           # both on: probability of CutMix (else Mixup)
     bucket_mb: float = 16.0                # gradient all-reduce bucket size (MiB)
     grad_comm_dtype: str = "fp32"          # fp32 | bf16 (wire dtype of the gradient all-reduce)
     overlap_comm: bool = True              # launch bucket all-reduce during backward
@@ -130,6 +136,10 @@ class Config:
             raise ValueError("aug_scale_min must be in (0, 1]")
         if not 0.0 <= self.label_smoothing <= 1.0:
             raise ValueError("label_smoothing must be in [0, 1]")
+        if not (self.mixup_alpha >= 0.0 and self.cutmix_alpha >= 0.0):
+            raise ValueError("mixup_alpha and cutmix_alpha must be >= 0 (0 = off)")
+        if not (0.0 <= self.mix_prob <= 1.0 and 0.0 <= self.mix_switch_prob <= 1.0):
+            raise ValueError("mix_prob and mix_switch_prob must be in [0, 1]")
         if self.eval_topk < 0:
             raise ValueError("eval_topk must be >= 0 (0 or 1 = top-1 only)")
 
@@ -147,6 +157,15 @@ class Config:
         if self.augment == "none":
             return None
         return dict(kind=self.augment, scale_min=self.aug_scale_min, seed=self.seed)
+
+    @property
+    def mix_spec(self) -> Optional[Dict[str, Any]]:
+        """The training loader's ``mix`` argument (None when both alphas are 0).  The seed is
+        the run's; the batch a sample sits in (and so its partner) is the rank's."""
+        if self.mixup_alpha == 0.0 and self.cutmix_alpha == 0.0:
+            return None
+        return dict(mixup_alpha=self.mixup_alpha, cutmix_alpha=self.cutmix_alpha,
+                    prob=self.mix_prob, switch_prob=self.mix_switch_prob, seed=self.seed)
 
     @property
     def input_hw(self):

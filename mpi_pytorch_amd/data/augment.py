@@ -11,6 +11,12 @@ batch.  ``id`` is stable per sample (:func:`sample_ids`: crc32 of the file name,
 ``SyntheticImages`` already uses), so a sample's box and flip depend on nothing but
 ``(seed, epoch, id, extent)`` - not on its batch, its position in the batch, the batch
 size or the number of ranks.
+
+Mixup / CutMix (:func:`sample_mix`) pair every sample with the next one of its batch, so
+their parameters belong to the batch: one generator per call, keyed by ``(seed, epoch, the
+ids in batch order)`` and dropped afterwards.  The preprocess launch blends the images
+(``Fn.preprocess(mix=, lam=)``) and the fused cross-entropy the labels
+(:func:`label_weights`).
 """
 from __future__ import annotations
 
@@ -112,3 +118,67 @@ def sample_boxes(ids, extents, epoch: int, seed: int, scale=(0.08, 1.0),
         out[hit, 0], out[hit, 1], out[hit, 2], out[hit, 3] = y0[hit], x0[hit], hh[hit], ww[hit]
         out[~hit, :4] = fb
         return out
+
+
+def _mix_draws(ids, epoch: int, seed: int, mixup_alpha: float, cutmix_alpha: float,
+               prob: float, switch_prob: float):
+    """The per-sample draws of :func:`sample_mix`: (mixed, cut) bool [B], beta [B] (Mixup's
+    lam or CutMix's l0; 1 where neither applies) and the rectangle centres (uy, ux) in
+    [0, 1).  Always the same number of draws in the same order, whatever the arguments."""
+    ids = np.ascontiguousarray(np.asarray(ids).astype(np.uint32).reshape(-1))
+    B = ids.shape[0]
+    rng = np.random.default_rng([int(seed) & 0xFFFFFFFF, int(epoch) & 0xFFFFFFFF,
+                                 zlib.crc32(ids.tobytes()), B])
+    u_use, u_cut, uy, ux = rng.random((4, B))
+    b_mix = rng.beta(mixup_alpha, mixup_alpha, B) if mixup_alpha > 0 else np.ones(B)
+    b_cut = rng.beta(cutmix_alpha, cutmix_alpha, B) if cutmix_alpha > 0 else np.ones(B)
+    mixed = (u_use < prob) & (mixup_alpha > 0 or cutmix_alpha > 0)
+    if mixup_alpha > 0 and cutmix_alpha > 0:
+        cut = mixed & (u_cut < switch_prob)
+    else:
+        cut = mixed & (cutmix_alpha > 0)
+    beta = np.where(cut, b_cut, np.where(mixed, b_mix, 1.0))
+    return mixed, cut, beta, uy, ux
+
+
+def sample_mix(ids, epoch: int, seed: int, out_hw, mixup_alpha: float, cutmix_alpha: float,
+               prob: float = 1.0, switch_prob: float = 0.5) -> Tuple[np.ndarray, np.ndarray]:
+    """``(mix int32 [B, 5], lam float32 [B])`` for ``Fn.preprocess(mix=, lam=)``: rows
+    (partner, y0, x0, h, w) with the rectangle in pixels of the (OH, OW) output.
+
+    partner: the next sample of the batch, ``(i + 1) % B``.  Per sample, with probability
+    ``1 - prob`` nothing (lam 1, no rectangle); otherwise CutMix with probability
+    ``switch_prob`` and Mixup otherwise when both alphas are > 0, or the one that is on.
+    Mixup: lam ~ Beta(a, a), no rectangle.  CutMix: l0 ~ Beta(a, a), r = sqrt(1 - l0), a
+    rectangle of sides int(OH * r), int(OW * r) around a centre uniform over the image,
+    clipped to the image; lam is 1 (the rectangle does the mixing) and the label's weight is
+    the area that stays (:func:`label_weights`).  A function of (seed, epoch, ids in batch
+    order, arguments) only: no generator state outlives the call."""
+    if mixup_alpha < 0 or cutmix_alpha < 0:
+        raise ValueError("sample_mix: alphas must be >= 0")
+    if not (0.0 <= prob <= 1.0 and 0.0 <= switch_prob <= 1.0):
+        raise ValueError("sample_mix: probabilities must be in [0, 1]")
+    OH, OW = int(out_hw[0]), int(out_hw[1])
+    mixed, cut, beta, uy, ux = _mix_draws(ids, epoch, seed, mixup_alpha, cutmix_alpha, prob,
+                                          switch_prob)
+    B = beta.shape[0]
+    mix = np.zeros((B, 5), dtype=np.int32)
+    mix[:, 0] = (np.arange(B) + 1) % max(B, 1)
+    r = np.sqrt(1.0 - beta)
+    h, w = (OH * r).astype(np.int64), (OW * r).astype(np.int64)
+    cy, cx = (uy * OH).astype(np.int64), (ux * OW).astype(np.int64)
+    y0, y1 = np.clip(cy - h // 2, 0, OH), np.clip(cy + h // 2, 0, OH)
+    x0, x1 = np.clip(cx - w // 2, 0, OW), np.clip(cx + w // 2, 0, OW)
+    box = cut & (y1 > y0) & (x1 > x0)
+    mix[box, 1], mix[box, 2] = y0[box], x0[box]
+    mix[box, 3], mix[box, 4] = (y1 - y0)[box], (x1 - x0)[box]
+    lam = np.where(mixed & ~cut, beta, 1.0).astype(np.float32)
+    return mix, lam
+
+
+def label_weights(mix: np.ndarray, lam: np.ndarray, out_hw) -> np.ndarray:
+    """float32 [B]: the weight of each sample's own label under :func:`sample_mix`'s rows -
+    Mixup: lam; CutMix: ``1 - area / (OH * OW)`` of the clipped rectangle; unmixed: 1."""
+    area = mix[:, 3].astype(np.float64) * mix[:, 4].astype(np.float64)
+    keep = 1.0 - area / float(int(out_hw[0]) * int(out_hw[1]))
+    return np.where(area > 0, keep, lam.astype(np.float64)).astype(np.float32)

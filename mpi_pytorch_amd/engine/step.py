@@ -21,7 +21,7 @@ from __future__ import annotations
 import contextlib
 import gc
 import os
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import torch
 import torch.nn as nn
@@ -44,17 +44,29 @@ def build_model(name: str, num_classes: int, feature_extract: bool, device: torc
     return model, input_size
 
 
+class MixedLabels(NamedTuple):
+    """The labels of a mixed batch (Mixup / CutMix): row r's target is ``lam[r]`` of
+    ``labels[r]`` and ``1 - lam[r]`` of ``labels2[r]`` (int64, int64, float32, all [B] on the
+    device)."""
+    labels: torch.Tensor
+    labels2: torch.Tensor
+    lam: torch.Tensor
+
+
 def loss_fn(out, labels, acc=None, label_smoothing=0.0):
     """CE; Inception's train-mode (logits, aux) uses loss + 0.4 * aux_loss (the documented
     fix of the reference's broken Inception path), one fused native op.
+    ``labels``: a label tensor, or :class:`MixedLabels` (every head mixes the same way);
     ``acc``: device scalar the loss is also added to (the trainer's running sum);
     ``label_smoothing``: torch's ``label_smoothing``, applied to every head."""
+    kw = dict(acc=acc, label_smoothing=label_smoothing)
+    if isinstance(labels, MixedLabels):
+        labels, kw["labels2"], kw["lam"] = labels
     if isinstance(out, (tuple, InceptionOutputs)):
         logits, aux = out[0], out[1]
         heads = [(aux, 0.4)] if aux is not None else None
-        return Fn.cross_entropy(logits, labels, acc=acc, heads=heads,
-                                label_smoothing=label_smoothing)
-    return Fn.cross_entropy(out, labels, acc=acc, label_smoothing=label_smoothing)
+        return Fn.cross_entropy(logits, labels, heads=heads, **kw)
+    return Fn.cross_entropy(out, labels, **kw)
 
 
 # MPA_WGRAD_STREAM_DDP=1: side-stream weight gradients with several ranks too (the bucket
@@ -275,12 +287,19 @@ class TrainStep:
         return loss.detach()
 
     def __call__(self, x, y) -> torch.Tensor:
-        if self._graph is not None and x.shape == self._static_x.shape:
+        """``y``: a label tensor or :class:`MixedLabels`.  A captured graph is replayed only
+        for the batch shape and the label kind it was captured with."""
+        if (self._graph is not None and x.shape == self._static_x.shape
+                and isinstance(y, MixedLabels) == isinstance(self._static_y, MixedLabels)):
             self._static_x.copy_(x)
-            self._static_y.copy_(y)
+            if isinstance(y, MixedLabels):  # all three are re-read by the replayed kernels
+                for dst, src in zip(self._static_y, y):
+                    dst.copy_(src)
+            else:
+                self._static_y.copy_(y)
             self._graph.replay()
             loss = self._static_loss
-        else:  # eager (also a short last batch of a graph-captured loop)
+        else:  # eager (also a short last batch, or the other label kind, of a captured loop)
             loss = self._eager(x, y)
             if self.world.world_size > 1 and tuple(x.shape) not in self._agreed:
                 # the first step of a batch shape tuned its GEMM tiles per rank: adopt
@@ -338,7 +357,8 @@ class TrainStep:
         if self.world.world_size != 1 or not x.is_cuda:
             return False
         self._static_x = x.clone()
-        self._static_y = y.clone()
+        self._static_y = (MixedLabels(*(t.clone() for t in y)) if isinstance(y, MixedLabels)
+                          else y.clone())
         self.timer = None  # replayed steps are not phase-timed
         snap = self.snapshot()
         s = torch.cuda.Stream()

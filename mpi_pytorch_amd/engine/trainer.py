@@ -36,14 +36,14 @@ from ..parallel.watchdog import Watchdog
 from ..data.manifest import (read_manifests, synthetic_manifest, SyntheticImages, FolderImages,
                              images_available)
 from ..data.loader import IMAGENET_MEAN, IMAGENET_STD
-from ..data.augment import sample_boxes, sample_ids
+from ..data.augment import sample_boxes, sample_ids, sample_mix, label_weights
 from ..ops import functional as Fn
 from ..parallel import (init_world, get_world, barrier, scatter_object, broadcast_object,
                         all_gather_object,
                         shard_dataframe, array_split_sizes, replica_checksum)
 from ..parallel.sharding import equal_step_count
 from ..utils.logging import init_logger, MetricsWriter, log_rank_lines
-from .step import build_training, steps_without_gc
+from .step import build_training, steps_without_gc, MixedLabels
 from ..models import input_spec
 
 
@@ -58,11 +58,17 @@ class ManifestBatches:
     ``augment`` (training loader only; ``Config.augment_spec``): a dict ``kind`` = "rrc"
     (random-resized crop + horizontal flip) or "flip", ``scale_min``, ``seed``.  Each batch
     then carries one crop box and flip bit per image (``data/augment.py``, keyed by the
-    epoch and the file name) into the same preprocess launch."""
+    epoch and the file name) into the same preprocess launch.
+
+    ``mix`` (training loader only; ``Config.mix_spec``): a dict ``mixup_alpha``,
+    ``cutmix_alpha``, ``prob``, ``switch_prob``, ``seed``.  Each batch then also carries one
+    row (partner, rectangle) and weight per image (``data/augment.py::sample_mix``, keyed by
+    the epoch and the batch's file names) into the same preprocess launch, and is yielded as
+    ``(x, MixedLabels(labels, labels[partner], label weight))``."""
 
     def __init__(self, names: Sequence[str], labels: Sequence[int], batch: int, out_hw,
                  device, source, shuffle: bool, seed: int = 0, mode: int = 0, cpad: int = 8,
-                 pad=None, augment=None):
+                 pad=None, augment=None, mix=None):
         self.names = list(names)
         self.labels = np.asarray(labels, dtype=np.int64)
         self.batch = batch
@@ -80,6 +86,10 @@ class ManifestBatches:
                 raise ValueError("augment kind must be rrc|flip")
             if mode != 0:
                 raise ValueError("augment needs mode 0 (the bilinear train transform)")
+        self.mix = dict(mix) if mix else None
+        if self.mix is not None and mode != 0:
+            raise ValueError("mix needs mode 0 (the bilinear train transform)")
+        if self.augment is not None or self.mix is not None:
             self.ids = sample_ids(self.names)
         self.pool = ThreadPoolExecutor(max_workers=1)
 
@@ -112,14 +122,37 @@ class ManifestBatches:
                             scale=(float(a.get("scale_min", 0.08)), 1.0),
                             crop=a["kind"] == "rrc")
 
+    def _mix(self, idx, epoch):
+        """``(mix, lam)`` of the batch ``idx`` in ``epoch`` for the preprocess launch, or
+        ``(None, None)`` without mixing."""
+        m = self.mix
+        if m is None:
+            return None, None
+        return sample_mix(self.ids[idx], epoch, int(m.get("seed", 0)), self.out_hw,
+                          float(m.get("mixup_alpha", 0.0)), float(m.get("cutmix_alpha", 0.0)),
+                          float(m.get("prob", 1.0)), float(m.get("switch_prob", 0.5)))
+
+    def _labels(self, labels, mix, lam):
+        """The batch's labels on the device; mixed: ``MixedLabels`` with the partners' labels
+        and the label weights."""
+        cuda = self.device.type == "cuda"
+        y = labels.to(self.device, non_blocking=cuda)
+        if mix is None:
+            return y
+        y2 = labels[torch.from_numpy(mix[:, 0].astype(np.int64))]
+        w = torch.from_numpy(label_weights(mix, lam, self.out_hw))
+        return MixedLabels(y, y2.to(self.device, non_blocking=cuda),
+                           w.to(self.device, non_blocking=cuda))
+
     def _to_device(self, imgs, labels, idx=None, epoch=0):
         cuda = self.device.type == "cuda"
+        mix, lam = self._mix(idx, epoch)
         if self._device_synth:
             imgs = self.source.load_device(imgs, self.device)
             x = Fn.preprocess(imgs, self.out_hw, IMAGENET_MEAN, IMAGENET_STD, self.mode,
                               self.cpad, out_dtype=torch.float32, pad=self.pad,
-                              boxes=self._boxes(idx, epoch, imgs.shape[1:3]))
-            return x, labels.to(self.device, non_blocking=True)
+                              boxes=self._boxes(idx, epoch, imgs.shape[1:3]), mix=mix, lam=lam)
+            return x, self._labels(labels, mix, lam)
         ext = None
         if not isinstance(imgs, np.ndarray):
             # decoded JPEGs of different sizes: one padded batch with per-image extents,
@@ -132,9 +165,9 @@ class ManifestBatches:
         x = Fn.preprocess(g, self.out_hw, IMAGENET_MEAN, IMAGENET_STD, self.mode, self.cpad,
                           out_dtype=torch.float32, pad=self.pad, extents=ext,
                           boxes=self._boxes(idx, epoch,
-                                            ext if ext is not None else imgs.shape[1:3]))
-        y = labels.to(self.device, non_blocking=cuda)
-        return x, y
+                                            ext if ext is not None else imgs.shape[1:3]),
+                          mix=mix, lam=lam)
+        return x, self._labels(labels, mix, lam)
 
     def epoch(self, e: int, steps: Optional[int] = None):
         order = np.arange(len(self.names))
@@ -193,7 +226,7 @@ def run_training(cfg: Config) -> dict:
     dev = world.device
     train_loader = ManifestBatches(my["file_name"].values, my["category_id"].values,
                                    cfg.BATCH_SIZE, out_hw, dev, source, True, cfg.seed + rank,
-                                   augment=cfg.augment_spec)
+                                   augment=cfg.augment_spec, mix=cfg.mix_spec)
     log.info("_Training Dataset Object Created")
     log.info("_Training Loader Created")
     val_loader = None
@@ -245,6 +278,9 @@ def run_training(cfg: Config) -> dict:
     log.info("_Model loaded to CPU")
     log.debug("_Compute device: %s", dev)  # (no such line in the reference)
     log.info("_Entering training Loop")
+    if cfg.mix_spec is not None:  # (no such line in the reference)
+        log.info("_Sample mixing: mixup_alpha {} | cutmix_alpha {} | prob {} | switch_prob {}"
+                 .format(cfg.mixup_alpha, cfg.cutmix_alpha, cfg.mix_prob, cfg.mix_switch_prob))
 
     if cfg.step_timers:
         step.enable_timers()
@@ -294,6 +330,9 @@ def run_training(cfg: Config) -> dict:
             tr = sorted(opt.last_trust_ratios().values())
             if tr:
                 rec["trust_ratio"] = {"min": tr[0], "median": tr[len(tr) // 2], "max": tr[-1]}
+        if cfg.mix_spec is not None:
+            rec["config"] = dict(mixup_alpha=cfg.mixup_alpha, cutmix_alpha=cfg.cutmix_alpha,
+                                 mix_prob=cfg.mix_prob, mix_switch_prob=cfg.mix_switch_prob)
         if step.timer is not None:
             rec["phases_ms"] = step.timer.summary()
         if size > 1:

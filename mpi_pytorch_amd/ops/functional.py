@@ -1302,45 +1302,55 @@ class _CrossEntropy(torch.autograd.Function):
     by its weight - no elementwise ATen ops for Inception's ``loss + 0.4 * aux_loss``."""
 
     @staticmethod
-    def forward(ctx, labels, weights, acc, smoothing, *logits):
+    def forward(ctx, labels, weights, acc, smoothing, mix, *logits):
         k = K(logits[0])
         out = torch.empty(1, device=logits[0].device, dtype=torch.float32)
-        lses = [k.ce_fwd_weighted(lg, labels, out, _or_empty(acc, lg), float(w), i > 0, smoothing)
+        lses = [k.ce_fwd_weighted(lg, labels, out, _or_empty(acc, lg), float(w), i > 0, smoothing,
+                                  *mix)
                 for i, (lg, w) in enumerate(zip(logits, weights))]
         ctx.weights = weights
         ctx.smoothing = smoothing  # one eps for every head, as a torch criterion applies it
-        ctx.save_for_backward(labels, *logits, *lses)
+        ctx.mixed = bool(mix)      # ... and one (labels2, lam): the aux head mixes the same way
+        ctx.save_for_backward(labels, *mix, *logits, *lses)
         return out.reshape(())
 
     @staticmethod
     def backward(ctx, go):
         saved = ctx.saved_tensors
-        labels, n = saved[0], len(ctx.weights)
-        logits, lses = saved[1:1 + n], saved[1 + n:]
+        labels, rest, n = saved[0], saved[1:], len(ctx.weights)
+        mix = rest[:2] if ctx.mixed else ()
+        rest = rest[len(mix):]
+        logits, lses = rest[:n], rest[n:]
         go = go.reshape(1).float().contiguous()
-        gs = [K(lg).ce_bwd(lg, labels, lse, go, float(w), ctx.smoothing)
+        gs = [K(lg).ce_bwd(lg, labels, lse, go, float(w), ctx.smoothing, *mix)
               for lg, lse, w in zip(logits, lses, ctx.weights)]
-        return (None, None, None, None) + tuple(gs)
+        return (None, None, None, None, None) + tuple(gs)
 
 
 def cross_entropy(logits, labels, weight: float = 1.0, acc: Optional[torch.Tensor] = None,
-                  heads=None, label_smoothing: float = 0.0):
+                  heads=None, label_smoothing: float = 0.0, labels2=None, lam=None):
     """Mean softmax cross-entropy (``nn.CrossEntropyLoss()`` at main.py:134,150).
 
     ``heads``: extra (logits, weight) terms summed into the same loss (Inception aux);
     ``acc``: a float32 device scalar the loss is also added to (no host sync);
-    ``label_smoothing``: torch's ``label_smoothing`` in [0, 1], applied to every head."""
+    ``label_smoothing``: torch's ``label_smoothing`` in [0, 1], applied to every head;
+    ``labels2`` / ``lam`` (int64 / float32 [B] on the logits' device; Mixup / CutMix): row
+    r's target is lam[r] * onehot(labels[r]) + (1 - lam[r]) * onehot(labels2[r]), for every
+    head; lam is read on the device, so a captured graph replays with new weights."""
     eps = float(label_smoothing)
     if not 0.0 <= eps <= 1.0:
         raise ValueError("label_smoothing must be in [0, 1], got %r" % (label_smoothing,))
+    if (labels2 is None) != (lam is None):
+        raise ValueError("cross_entropy: labels2 and lam go together")
+    mix = () if labels2 is None else (labels2, lam)
     lg = [logits] + [h[0] for h in (heads or [])]
     ws = (float(weight),) + tuple(float(h[1]) for h in (heads or []))
     if torch.is_grad_enabled() and any(t.requires_grad for t in lg):
-        return _CrossEntropy.apply(labels, ws, acc, eps, *lg)
+        return _CrossEntropy.apply(labels, ws, acc, eps, mix, *lg)
     k = K(logits)
     out = torch.empty(1, device=logits.device, dtype=torch.float32)
     for i, (t, w) in enumerate(zip(lg, ws)):
-        k.ce_fwd_weighted(t, labels, out, _or_empty(acc, t), w, i > 0, eps)
+        k.ce_fwd_weighted(t, labels, out, _or_empty(acc, t), w, i > 0, eps, *mix)
     return out.reshape(())
 
 
@@ -1355,7 +1365,7 @@ def count_topk(logits, labels, k: int, count: torch.Tensor) -> None:
 
 
 def preprocess(img_u8, out_hw, mean, std, mode: int = 0, cpad: int = 3,
-               out_dtype=torch.bfloat16, pad=None, extents=None, boxes=None):
+               out_dtype=torch.bfloat16, pad=None, extents=None, boxes=None, mix=None, lam=None):
     """u8 [B,H,W,3] -> resized, normalized NHWC with ``cpad`` channels, optionally on a
     zero-bordered canvas ``pad`` = (top, bottom, left, right) (the pre-padded input layout
     of a pixel-pair stem, ``models.layers.Conv2d.input_spec``).
@@ -1369,7 +1379,14 @@ def preprocess(img_u8, out_hw, mean, std, mode: int = 0, cpad: int = 3,
     from that crop of its slot instead of its whole extent (same arithmetic as resizing
     the contiguous crop) and the result is mirrored along W when flip is 1: random-resized
     crop + horizontal flip in the same launch (``data/augment.py`` samples the rows).  A
-    box outside its image's extent raises ``ValueError`` here; the kernel does not check."""
+    box outside its image's extent raises ``ValueError`` here; the kernel does not check.
+    ``mix`` (host int [B, 5]) and ``lam`` (host float [B]), mode 0, both or neither - Mixup /
+    CutMix in the same launch: rows (partner, y0, x0, h, w) name an image of the same batch
+    and a rectangle in output pixels (inside the canvas border; h or w 0: none).  With P
+    the launch's result without them, image b becomes P[partner] inside its rectangle and
+    bf16(lam * P[b] + (1 - lam) * P[partner]) outside it, bitwise that fp32 expression of the
+    bf16 values (``data/augment.py::sample_mix`` draws the rows).  Bad rows raise
+    ``ValueError`` here; the kernel does not check."""
     k = K(img_u8)
     pad = list(pad) if pad else []
     if extents is not None:
@@ -1381,6 +1398,8 @@ def preprocess(img_u8, out_hw, mean, std, mode: int = 0, cpad: int = 3,
                              % (extents.tolist(), Hp, Wp))
     if boxes is not None:
         boxes = _check_boxes(boxes, extents, img_u8.shape, mode)
+    if mix is not None or lam is not None:
+        mix, lam = _check_mix(mix, lam, img_u8.shape[0], out_hw, mode)
     if img_u8.is_cuda:
         if mode == 1:  # PIL-exact bicubic (the eval transform)
             tc = _PIL_TABLES.get(img_u8.device)
@@ -1396,17 +1415,61 @@ def preprocess(img_u8, out_hw, mean, std, mode: int = 0, cpad: int = 3,
         ext = None
         if extents is not None:
             ext = torch.from_numpy(extents.astype(np.int32)).to(img_u8.device, non_blocking=True)
+        if mix is not None:
+            if boxes is None:  # the mixed kernel takes boxes: the full extents
+                B, Hp, Wp = img_u8.shape[:3]
+                boxes = np.zeros((B, 5), np.int32)
+                boxes[:, 2:4] = extents if extents is not None else (Hp, Wp)
+            dev = img_u8.device
+            return k.preprocess(img_u8, out_hw[0], out_hw[1], list(mean), list(std), mode, cpad,
+                                pad, ext, box=torch.from_numpy(boxes).to(dev, non_blocking=True),
+                                mix=torch.from_numpy(mix).to(dev, non_blocking=True),
+                                lam=torch.from_numpy(lam).to(dev, non_blocking=True))
         if boxes is not None:
             box = torch.from_numpy(boxes).to(img_u8.device, non_blocking=True)
             return k.preprocess(img_u8, out_hw[0], out_hw[1], list(mean), list(std), mode, cpad,
                                 pad, ext, box=box)
         return k.preprocess(img_u8, out_hw[0], out_hw[1], list(mean), list(std), mode, cpad, pad,
                             ext)
+    if mix is not None:
+        return k.preprocess(img_u8, out_hw[0], out_hw[1], list(mean), list(std), mode, cpad,
+                            out_dtype, pad, extents, boxes, mix, lam)
     if boxes is not None:
         return k.preprocess(img_u8, out_hw[0], out_hw[1], list(mean), list(std), mode, cpad,
                             out_dtype, pad, extents, boxes)
     return k.preprocess(img_u8, out_hw[0], out_hw[1], list(mean), list(std), mode, cpad,
                         out_dtype, pad, extents)
+
+
+def _check_mix(mix, lam, B, out_hw, mode):
+    """Mixing rows (partner, y0, x0, h, w) as a contiguous int32 [B, 5] array and the weights
+    as float32 [B], or ``ValueError``: partners in [0, B), rectangles inside [0, OH] x [0, OW]
+    with non-negative sides, weights finite and in [0, 1].  This host check is all that keeps
+    the kernel's reads inside the batch."""
+    if mode != 0:
+        raise ValueError("preprocess: mixing needs mode 0 (the bilinear train transform)")
+    if mix is None or lam is None:
+        raise ValueError("preprocess: mix and lam go together")
+    B, (OH, OW) = int(B), (int(v) for v in out_hw)
+    mx, lm = np.asarray(mix), np.asarray(lam)
+    if mx.dtype.kind not in "iu" or mx.shape != (B, 5):
+        raise ValueError("preprocess: mix must be an integer [%d, 5] array, got %s %s"
+                         % (B, mx.dtype, mx.shape))
+    if lm.dtype.kind != "f" or lm.shape != (B,):
+        raise ValueError("preprocess: lam must be a float [%d] array, got %s %s"
+                         % (B, lm.dtype, lm.shape))
+    mx = mx.astype(np.int64)
+    p, y0, x0, h, w = (mx[:, i] for i in range(5))
+    bad = (p < 0) | (p >= B) | (h < 0) | (w < 0) | (y0 < 0) | (x0 < 0) | (y0 + h > OH) \
+        | (x0 + w > OW)
+    if bad.any():
+        b = int(np.argmax(bad))
+        raise ValueError("preprocess: mix row %s of image %d: partner outside [0, %d) or "
+                         "rectangle outside the (%d, %d) output (rows are partner, y0, x0, h, w)"
+                         % (mx[b].tolist(), b, B, OH, OW))
+    if not (np.isfinite(lm).all() and (lm >= 0.0).all() and (lm <= 1.0).all()):
+        raise ValueError("preprocess: lam must be finite and in [0, 1]")
+    return np.ascontiguousarray(mx.astype(np.int32)), np.ascontiguousarray(lm.astype(np.float32))
 
 
 def _check_boxes(boxes, extents, shape, mode) -> np.ndarray:

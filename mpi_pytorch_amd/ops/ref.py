@@ -544,11 +544,16 @@ def linear_wgrad(dy, x, dw, overwrite=False):
 
 
 # --------------------------------------------------------------------------- loss / acc
-def ce_fwd(logits, labels, smoothing=0.0):
-    """``smoothing``: torch's ``label_smoothing`` - the target is (1 - eps) * onehot + eps / NC."""
+def ce_fwd(logits, labels, smoothing=0.0, labels2=None, lam=None):
+    """``smoothing``: torch's ``label_smoothing`` - the target is (1 - eps) * onehot + eps / NC.
+    ``labels2`` / ``lam`` [B] (Mixup / CutMix): onehot is lam * onehot(labels) + (1 - lam) *
+    onehot(labels2)."""
     lf = _f(logits)
     lse = torch.logsumexp(lf, dim=1)
     picked = lf.gather(1, labels.view(-1, 1).long()).squeeze(1)
+    if labels2 is not None:
+        lam = _f(lam)
+        picked = lam * picked + (1.0 - lam) * lf.gather(1, labels2.view(-1, 1).long()).squeeze(1)
     if smoothing:
         rows = lse - (1.0 - smoothing) * picked - (smoothing / lf.shape[1]) * lf.sum(1)
     else:
@@ -556,17 +561,26 @@ def ce_fwd(logits, labels, smoothing=0.0):
     return rows.mean().reshape(1), lse
 
 
-def ce_bwd(logits, labels, lse, grad_out, weight=1.0, smoothing=0.0):
+def ce_bwd(logits, labels, lse, grad_out, weight=1.0, smoothing=0.0, labels2=None, lam=None):
     B, NC = logits.shape
     p = torch.exp(_f(logits) - lse[:, None])
     if smoothing:
         p -= smoothing / NC
-    p[torch.arange(B, device=logits.device), labels.long()] -= 1.0 - smoothing
+    rows = torch.arange(B, device=logits.device)
+    if labels2 is not None:  # the two weights are added first: right, and the same under a
+        lam = _f(lam)        # swap of the labels, when both name one column
+        w = torch.zeros_like(p)
+        w[rows, labels.long()] += lam
+        w[rows, labels2.long()] += 1.0 - lam
+        p -= (1.0 - smoothing) * w
+    else:
+        p[rows, labels.long()] -= 1.0 - smoothing
     return (p * (_f(grad_out).reshape(()) * weight / B)).to(logits.dtype)
 
 
-def ce_fwd_weighted(logits, labels, out, acc, weight, accumulate, smoothing=0.0):
-    loss, lse = ce_fwd(logits, labels, smoothing)
+def ce_fwd_weighted(logits, labels, out, acc, weight, accumulate, smoothing=0.0, labels2=None,
+                    lam=None):
+    loss, lse = ce_fwd(logits, labels, smoothing, labels2, lam)
     v = loss.reshape(1) * weight
     if accumulate:
         out[:1] += v
@@ -852,7 +866,7 @@ def lars_step_dev(master, grad, buf, shadow, step_t, hyper, seg, chunk_seg, rati
 
 # ------------------------------------------------------------------------ preprocessing
 def preprocess(img_u8, oh, ow, mean, std, mode, cpad, out_dtype, pad=None, extents=None,
-               boxes=None):
+               boxes=None, mix=None, lam=None):
     """u8 NHWC [B,H,W,3] -> normalized NHWC [B,oh,ow,cpad] (zero padded channels), on a
     zero-bordered canvas when pad = (top, bottom, left, right).
 
@@ -865,7 +879,31 @@ def preprocess(img_u8, oh, ow, mean, std, mode, cpad, out_dtype, pad=None, exten
     boxes (mode 0): rows (y0, x0, h, w, flip); image b is the resize of its crop
     [y0:y0+h, x0:x0+w], mirrored along W when flip is set (RandomResizedCrop ->
     RandomHorizontalFlip: the mirror of the resize's result, inside the canvas border).
+    mix / lam (mode 0; Mixup / CutMix): rows (partner, y0, x0, h, w) and weights [B].  With
+    P the un-mixed result in ``out_dtype``, image b is P[partner] inside its rectangle (output
+    pixels, inside the canvas border) and lam * P[b] + (1 - lam) * P[partner] outside it,
+    evaluated in fp32 (P[b] / P[partner] themselves at lam 1 / 0), then cast to ``out_dtype``.
     """
+    if mix is not None:
+        assert mode == 0 and lam is not None, "mix: mode 0 only, with lam"
+        P = preprocess(img_u8, oh, ow, mean, std, mode, cpad, out_dtype, pad, extents, boxes)
+        t, _bo, l, _r = pad if pad else (0, 0, 0, 0)
+        out = P.clone()
+        lam_h = torch.as_tensor(lam).detach().cpu().float()  # (float32 weights, as the kernel's)
+        for b, (pb, y0, x0, h, w) in enumerate(torch.as_tensor(mix).tolist()):
+            own, other = P[b].float(), P[pb].float()
+            lb = lam_h[b]
+            if float(lb) == 1.0:
+                v = own.clone()
+            elif float(lb) == 0.0:
+                v = other.clone()
+            else:
+                v = lb * own + (1.0 - lb) * other
+            if h > 0 and w > 0:
+                v[t + y0:t + y0 + h, l + x0:l + x0 + w] = other[t + y0:t + y0 + h,
+                                                                l + x0:l + x0 + w]
+            out[b] = v.to(out_dtype)
+        return out
     if boxes is not None:
         assert mode == 0, "boxes: mode 0 only"
         parts = []

@@ -1,20 +1,26 @@
 """Time of the training preprocess launch (mode 0: bilinear resize + normalize -> bf16 NHWC),
-plain and with crop boxes (random-resized crop + flip in the same launch).
+plain, with crop boxes (random-resized crop + flip in the same launch) and mixed (Mixup /
+CutMix in the same launch).
 
     python tools/bench_preprocess.py --batch 256 --src 448 448 --out 224 224
     python tools/bench_preprocess.py --batch 2048 --src 224 224 --out 224 224
 
 Times the kernel launch alone (the binding, device-resident images and boxes) with HIP
 events: ``--iters`` back-to-back launches per timed window, ``--repeats`` windows after
-``--warmup`` launches.  Variants:
+``--warmup`` launches; every variant is warmed first and the windows then alternate between
+the variants, so all of them see the same state of the device.  Variants:
   plain       no boxes (the identity-size copy fast path where it applies)
   plain_bilinear  identity sizes only: no boxes with the copy fast path switched off, i.e.
               the bilinear kernel the boxed variants run - their like-for-like baseline
   full_boxes  every box the whole image, flip 0 (same output as plain, through the BOX kernel)
   rrc_boxes   boxes drawn by data/augment.py (scale_min .. 1, ratio 3/4 .. 4/3, flips)
+  mixup       rrc_boxes + a Mixup row per image (partner = the next image, lam ~ Beta(.2, .2)):
+              every output pixel reads two source images
+  cutmix      rrc_boxes + a CutMix row per image (alpha 1): the partner is read only by the
+              row groups its rectangle crosses
 Prints one JSON line per variant: microseconds per launch (median / min / max over the
 windows) and the source + output bytes the launch has to move.  A build without box
-support (an older checkout) reports the plain variant only."""
+support (an older checkout) reports the plain variant only, one without mixing no mixed rows."""
 import argparse
 import json
 import os
@@ -32,6 +38,10 @@ try:
     from mpi_pytorch_amd.data.augment import sample_boxes
 except ImportError:  # a build from before the augmentation
     sample_boxes = None
+try:
+    from mpi_pytorch_amd.data.augment import sample_mix
+except ImportError:  # a build from before the mixing
+    sample_mix = None
 
 
 def main():
@@ -64,22 +74,32 @@ def main():
         rrc = sample_boxes(np.arange(B), np.tile([[H, W]], (B, 1)), 0, 0,
                            scale=(a.scale_min, 1.0))
         variants += [("full_boxes", full), ("rrc_boxes", rrc)]
+        if sample_mix is not None:
+            variants += [("mixup", rrc), ("cutmix", rrc)]
+    runs = []
     for name, boxes in variants:
         kw = {}
         src_bytes = B * H * W * 3
         if boxes is not None:
             kw["box"] = torch.from_numpy(boxes).to(dev)
             src_bytes = int((boxes[:, 2].astype(np.int64) * boxes[:, 3]).sum()) * 3
+        if name in ("mixup", "cutmix"):
+            alphas = (0.2, 0.0) if name == "mixup" else (0.0, 1.0)
+            mix, lam = sample_mix(np.arange(B), 0, 0, (OH, OW), *alphas)
+            kw["mix"] = torch.from_numpy(mix).to(dev)
+            kw["lam"] = torch.from_numpy(lam).to(dev)
 
-        def launch():
+        def launch(kw=kw):
             return k.preprocess(img, OH, OW, mean, std, 0, a.cpad, pad, None, **kw)
 
+        runs.append((name, launch, src_bytes, []))
         k.preprocess_set_copy(0 if name == "plain_bilinear" else 1)
         for _ in range(a.warmup):
             launch()
-        torch.cuda.synchronize()
-        us = []
-        for _ in range(a.repeats):
+    torch.cuda.synchronize()
+    for _ in range(a.repeats):
+        for name, launch, _src, us in runs:
+            k.preprocess_set_copy(0 if name == "plain_bilinear" else 1)
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
             for _ in range(a.iters):
@@ -87,6 +107,8 @@ def main():
             e1.record()
             e1.synchronize()
             us.append(e0.elapsed_time(e1) * 1e3 / a.iters)
+    k.preprocess_set_copy(1)
+    for name, _launch, src_bytes, us in runs:
         med = statistics.median(us)
         print(json.dumps({"metric": "preprocess mode 0 us/launch", "tag": a.tag, "variant": name,
                           "batch": B, "src": [H, W], "out": [OH, OW], "cpad": a.cpad, "pad": pad,
