@@ -1980,6 +1980,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "halo weight gradients on producer-wave blocks on/off (MPA_HALO_WPROD)");
   m.def("igemm_set_halo_wxmap", &mpa::igemm_set_halo_wxmap,
         "XCD-grouped halo weight-gradient block order on/off (MPA_HALO_WXMAP)");
+  m.def("igemm_set_halo_trim", &mpa::igemm_set_halo_trim,
+        "geometry-sized halo fetch of the linear-tile 3x3 kernels on/off (A/B, tests)");
+  m.def("conv3_halo_dma_count", &mpa::conv3_halo_dma_count, py::arg("H"), py::arg("W"),
+        "planned halo DMAs per producer wave and item, 256-pixel forward / dgrad tiles");
+  m.def("conv3_halo_wgrad_dma_count", &mpa::conv3_halo_wgrad_dma_count, py::arg("H"),
+        py::arg("W"), "planned halo DMAs per wave and chunk, 4-wave weight-gradient tiles");
   m.def("affine_act", &affine_act, "relu?(x * aff[0] + aff[1]) per channel (aff [2, C])");
   m.def("conv_fwd", &conv_fwd, py::arg("x"), py::arg("w"), py::arg("bias"), py::arg("sh"),
         py::arg("sw"), py::arg("ph"), py::arg("pw"), py::arg("relu"), py::arg("stats"),

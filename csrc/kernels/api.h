@@ -204,6 +204,12 @@ void igemm_stem_pool_wgrad(WGradArgs a, StemPoolArgs q, hipStream_t s);
 bool conv3_halo_wgrad_ok(const WGradArgs& a);
 void igemm_set_halo_wxmap(int on);  // XCD-grouped halo weight-gradient blocks (MPA_HALO_WXMAP)
 void igemm_set_halo_wprod(int on);  // producer-wave halo weight gradients (MPA_HALO_WPROD)
+// Geometry-sized halo fetch of the linear-tile 3x3 kernels (default on; A/B and tests), and
+// the planned halo DMA instructions per wave for H x W images: 256-pixel forward / dgrad
+// tiles (of 9), 4-wave 128-pixel weight-gradient tiles (per chunk, of 7)
+void igemm_set_halo_trim(int on);
+int conv3_halo_dma_count(int H, int W);
+int conv3_halo_wgrad_dma_count(int H, int W);
 int conv3_halo_wgrad(WGradArgs a, hipStream_t s);
 int64_t conv3_halo_wgrad_ws_floats(int Kout, int Ncols);
 bool igemm_halo_enabled();

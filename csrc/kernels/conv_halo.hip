@@ -62,7 +62,18 @@ struct HaloPlan {
   uint32_t mag_w, mag_w2, mag_h1, mag_hw;  // floor(2^32 / d) + 1: exact n / d for n*d < 2^32
   int tiles_m, tiles_total, cc;
   uint32_t a_bytes, b_bytes;
+  int hiw;              // (256-pixel tiles) halo DMA instructions per producer wave and item:
+                        // the slots any tile of this geometry reads (halo_need), <= HB_HIW
 };
+
+// Zero an LDS range (16-B aligned, a multiple of 16 B) with the whole block; no barrier.
+// The halo stages are zeroed once per block: with a geometry-sized fetch (HaloPlan::hiw,
+// the weight gradient's HT) the slots past the fetch are never written, and a stale NaN
+// bit pattern there would survive a multiplication by a masked row's zero.
+__device__ __forceinline__ void lds_zero(char* lds, int bytes, int tid, int nthreads) {
+  for (int o = tid * 16; o < bytes; o += nthreads * 16)
+    *LDS_PTR(u32x4, lds + o) = u32x4{0u, 0u, 0u, 0u};
+}
 
 __device__ __forceinline__ bf16x8 frag16(const char* lds_byte) {
   return __builtin_bit_cast(bf16x8, *LDS_PTR(const u32x4, lds_byte));
@@ -308,6 +319,16 @@ __global__ __launch_bounds__(MI == 4 ? 512 : 256, 1) void conv3_halo_kernel(IGem
   const int nimg = p.M / HW;
   const int jq = lane >> 4, l15 = lane & 15;
 
+  if constexpr (!SELF) {  // (before any DMA is issued: see lds_zero)
+    lds_zero(hal, 2 * HBYTES, tid, 512);
+    __syncthreads();
+  }
+  // halo DMA instructions per producer wave and item; the slot blocks (16 slots, 1 KiB)
+  // are dealt round-robin, block j * 4 + wave, so a geometry-sized count h.hiw < HIW takes
+  // the same share off every producer (SELF: the whole stage, wave w's blocks w*HIW + j)
+  const int hiw = SELF ? HIW : h.hiw;
+  auto hblock = [&](int j) { return SELF ? wave * HIW + j : j * HB_NW + wave; };
+
   // persistent tile list: XCD x = blockIdx % 8 owns tiles [x*T/8, (x+1)*T/8); the host
   // makes G8 a multiple of tiles_n, so a block's tiles all share one column tile nt
   const int T = h.tiles_total;
@@ -327,7 +348,7 @@ __global__ __launch_bounds__(MI == 4 ? 512 : 256, 1) void conv3_halo_kernel(IGem
     uint32_t hsc[HIW];  // slot | (col + 1) << 10 | chunk << 18
 #pragma unroll
     for (int j = 0; j < HIW; ++j) {
-      const uint32_t hp = 16 * (wave * HIW + j) + (lane >> 2);
+      const uint32_t hp = 16 * hblock(j) + (lane >> 2);
       const uint32_t s = udiv(hp, h.mag_w2);
       const uint32_t colp = hp - s * W2;
       const uint32_t lc = (lane & 3) ^ (((hp >> 2) & 1) << 1);
@@ -368,8 +389,8 @@ __global__ __launch_bounds__(MI == 4 ? 512 : 256, 1) void conv3_halo_kernel(IGem
         const __amdgpu_buffer_rsrc_t ra = make_rsrc((const char*)p.A + cc * 64, h.a_bytes);
         // (SELF: as asm, invisible to the compiler, which would otherwise wait for these
         // DMAs before the MFMA waves' next ds_read of the other stage)
-        if constexpr (SELF) buf_lds16_asm(ra, hal + stage * HBYTES + (wave * HIW + j) * 1024, hv[j]);
-        else buf_lds16(ra, hal + stage * HBYTES + (wave * HIW + j) * 1024, hv[j]);
+        if constexpr (SELF) buf_lds16_asm(ra, hal + stage * HBYTES + hblock(j) * 1024, hv[j]);
+        else buf_lds16(ra, hal + stage * HBYTES + hblock(j) * 1024, hv[j]);
       } else if (!WRES && j < HIW + HB_WIW) {
         const __amdgpu_buffer_rsrc_t rb = make_rsrc((const char*)p.B + cc * 64, h.b_bytes);
         buf_lds16(rb, wst + stage * HB_WBYTES + (wave * HB_WIW + j - HIW) * 1024,
@@ -378,7 +399,8 @@ __global__ __launch_bounds__(MI == 4 ? 512 : 256, 1) void conv3_halo_kernel(IGem
     };
     auto issue = [&](int cc, int stage) {
 #pragma unroll
-      for (int j = 0; j < HIW + HB_WIW; ++j) dma(cc, stage, j);
+      for (int j = 0; j < HIW + HB_WIW; ++j)
+        if (j >= HIW || j < hiw) dma(cc, stage, j);  // (wave-uniform bound, as the strips')
     };
     if (nitems > 0) {
       if constexpr (WRES) {  // whole weight tile (tiles_n == 1, CC <= 2) once per block
@@ -1130,9 +1152,17 @@ struct HaloWPlan {
 // k's barrier publishes stage k & 1 and frees stage (k + 1) & 1.
 // KM: 16-row k fragments per partition (4; 2 when Kout == 32 - DenseNet's growth-rate
 // convs - so the partition's zero upper half costs no MFMA and no fragment read)
-template <int W2T, bool ONECH = false, bool STRIP = false, bool PROD = false, int KM = 4>
+// HT (4-wave linear tiles): halo DMA instructions per wave and chunk, sized on the host to
+// the slots a tile of the launch's geometry reads (halo_need; ResNet layer2 5, layer3 4 of
+// 7).  Compile-time, so the MFMA stream that carries the DMAs has no per-DMA branch; the
+// slot blocks are dealt round-robin (block j * 4 + wave), so every wave sheds the same share.
+template <int W2T, bool ONECH = false, bool STRIP = false, bool PROD = false, int KM = 4,
+          int HT = HW_HIW>
 __global__ __launch_bounds__(PROD ? 512 : 256, 1) void conv3_halo_wgrad_kernel(WGradArgs p, HaloWPlan h) {
-  constexpr int HIW = ONECH ? 2 * HW_HIW : HW_HIW;  // halo DMA instructions per wave (chunk)
+  constexpr bool RR = !ONECH && !STRIP && !PROD;  // round-robin slot blocks, HT per wave
+  static_assert(HT == HW_HIW || RR, "geometry-sized halo fetch: 4-wave linear tiles only");
+  static_assert(HT >= 1 && HT <= HW_HIW, "halo DMA count");
+  constexpr int HIW = ONECH ? 2 * HW_HIW : HT;  // halo DMA instructions per wave (chunk)
   __shared__ __attribute__((aligned(16))) char smem[HW_LDS];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave_all = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -1140,6 +1170,13 @@ __global__ __launch_bounds__(PROD ? 512 : 256, 1) void conv3_halo_wgrad_kernel(W
   const int H = p.H, W = p.W, HW = H * W, W2 = W2T ? W2T : h.w2, C = p.C, K = p.Kout;
   const int M = p.Mpix, nimg = M / HW;
   const int g = lane >> 4, li = lane & 15, q = li >> 2, pp = li & 3;
+
+  if constexpr (RR) {  // (before any DMA is issued: see lds_zero)
+    lds_zero(smem + HW_DBYTES, 2 * HW_HBYTES, tid, 256);
+    lds_zero(smem + HW_STAGE + HW_DBYTES, 2 * HW_HBYTES, tid, 256);
+    __syncthreads();
+  }
+  auto hblock = [&](int j) { return RR ? j * 4 + wave : wave * HIW + j; };
 
   const int bid = h.xmap ? (blockIdx.x & 7) * (gridDim.x >> 3) + (blockIdx.x >> 3) : blockIdx.x;
   const int part = bid % h.parts, z = bid / h.parts;
@@ -1159,12 +1196,12 @@ __global__ __launch_bounds__(PROD ? 512 : 256, 1) void conv3_halo_wgrad_kernel(W
     drow[j] = ((uint32_t)(STRIP ? 0 : row) * K + k0 + chunk * 8) * 2;
     kok[j] = k0 + chunk * 8 < K;
   }
-  // halo: instruction j = pixels 16 (7 wave + j) + lane/4 of the image; chunk 1 of the
+  // halo: instruction j = pixels 16 hblock(j) + lane/4 of the image; chunk 1 of the
   // partition is the same lanes with the descriptor base 64 B further
   uint32_t hsc[HIW];
 #pragma unroll
   for (int j = 0; j < HIW; ++j) {
-    const uint32_t hp = 16 * (wave * HIW + j) + (lane >> 2);
+    const uint32_t hp = 16 * hblock(j) + (lane >> 2);
     const uint32_t sl = udiv(hp, h.mag_w2);
     const uint32_t colp = hp - sl * W2;
     const uint32_t lc = (lane & 3) ^ (((hp >> 3) & 1) << 1);
@@ -1289,7 +1326,7 @@ __global__ __launch_bounds__(PROD ? 512 : 256, 1) void conv3_halo_wgrad_kernel(W
         }
     }
   };
-  // DMA instruction j of a tile: dy rows (0..3), halo chunk 0 (4..10), halo chunk 1 (11..17)
+  // DMA instruction j of a tile: dy rows (0..3), halo chunk 0 (4..3+HT), chunk 1 (..3+2HT)
   const uint32_t sw = lds_base(smem) + wave * 4096;  // this wave's DMA pieces: + 1 KiB each
   auto dmaw = [&](int stage, int j) {
     const uint32_t st = sw + stage * HW_STAGE;
@@ -1298,10 +1335,10 @@ __global__ __launch_bounds__(PROD ? 512 : 256, 1) void conv3_halo_wgrad_kernel(W
     } else if constexpr (ONECH) {
       const int jj = j - 4;
       buf_lds16_at(rx0, st - wave * 4096 + HW_DBYTES + (wave * HIW + jj) * 1024, hv[jj]);
-    } else {
-      const int ch = (j - 4) / HW_HIW, jj = (j - 4) % HW_HIW;
+    } else if (j < 4 + 2 * HT) {
+      const int ch = (j - 4) / HT, jj = (j - 4) % HT;
       buf_lds16_at(ch ? rx1 : rx0, st - wave * 4096 + HW_DBYTES + ch * HW_HBYTES +
-                                       (wave * HW_HIW + jj) * 1024, hv[jj]);
+                                       hblock(jj) * 1024, hv[jj]);
     }
   };
   auto issue = [&](int stage) {
@@ -1493,6 +1530,35 @@ int active_cus() {
 // border is the next row's left border), rounded up to 8 pixels
 static int halo_pitch(int W) { return (W + 1 + 7) / 8 * 8; }
 
+// Halo slots (pixels of pitch-P rows) that the taps of any linear tile of BM pixels reach:
+// the rows the tile touches, 2 halo rows and the image separators it crosses (+1: with
+// P == W + 1 the last slot's right border is the next pixel).  One expression for the
+// admission checks (the stage must hold it) and for the geometry-sized fetch (nothing at
+// or past it is read: tools/halo_index_check.py proves that for every tile).
+static int64_t halo_need(int BM, int H, int W, int P) {
+  const int64_t HW = (int64_t)H * W;
+  const int64_t rows = (BM - 1 + W - 1) / W + 1;
+  const int64_t seps = (BM - 1) / HW + 1;
+  return (rows + 2 + seps) * P + (P == W + 1 ? 1 : 0);
+}
+
+// Geometry-sized halo fetch (A/B and tests; off: every launch fetches the whole stage)
+static bool g_halo_trim = true;
+void igemm_set_halo_trim(int on) { g_halo_trim = on != 0; }
+
+// 16-slot DMA instructions per wave (4 DMA waves, slot blocks dealt round-robin) that
+// cover `need` slots, at most the stage's hiw_max
+static int halo_dma_count(int64_t need, int hiw_max) {
+  if (!g_halo_trim) return hiw_max;
+  const int64_t blocks = (need + 15) / 16;
+  return (int)std::min<int64_t>(hiw_max, (blocks + 3) / 4);
+}
+
+// the 256-pixel linear tiles' count for an H x W image (HaloPlan::hiw)
+int conv3_halo_dma_count(int H, int W) {
+  return halo_dma_count(halo_need(HB_BM, H, W, halo_pitch(W)), HB_HIW);
+}
+
 // epilogue flavour of a launch; -1: not instantiated (the implicit GEMM runs it)
 static int halo_epi(const IGemmArgs& a) {
   int e = 0;
@@ -1560,12 +1626,8 @@ static bool halo_ok_impl(const IGemmArgs& a, bool& linear) {
   if ((int64_t)a.N * a.ldb * 2 >= (1ll << 31)) return false;
   // (strip tiles only: shifted tap sets - valid convs and their dgrads - and wide images)
   if (ch != 0 || cw != 0 || HW + HB_BM >= 65536 || a.aW + 2 > 255) return true;
-  // halo slots of any 256-pixel tile: rows touched + 2 halo rows + image separators
-  const int64_t rows = (HB_BM - 1 + a.aW - 1) / a.aW + 1;
-  const int64_t seps = (HB_BM - 1) / HW + 1;
-  // (+1: with P == W + 1 the last slot's right border is the next pixel)
-  const int P = halo_pitch(a.aW);
-  linear = (rows + 2 + seps) * P + (P == a.aW + 1 ? 1 : 0) <= HB_HPX &&
+  // the halo slots of any 256-pixel tile must fit the stage
+  linear = halo_need(HB_BM, a.aH, a.aW, halo_pitch(a.aW)) <= HB_HPX &&
            (a.N % HB_BN == 0 || n32_lin);
   return true;
 }
@@ -1762,6 +1824,7 @@ int conv3_halo(IGemmArgs a, hipStream_t s) {
   h.mag_h1 = magic(a.aH + 1);
   h.mag_hw = magic(a.aH * a.aW);
   h.cc = a.aC / 32;
+  h.hiw = conv3_halo_dma_count(a.aH, a.aW);
   const bool wres = g_halo_wres && (a.N + HB_BN - 1) / HB_BN == 1 && h.cc <= 2;
   const bool mi7 = halo_mi7_ok(a, halo_epi(a), wres);
   h.tiles_m = mi7 ? a.M / 448 : (a.M + HB_BM - 1) / HB_BM;
@@ -1845,18 +1908,27 @@ static bool halo_wgrad_geom(const WGradArgs& a) {
   if (!halo_wgrad_base(a) || a.ph != 1 || a.pw != 1) return false;
   const int64_t HW = (int64_t)a.H * a.W;
   if (HW + HW_BM >= 65536 || a.W + 2 > 255) return false;
-  const int64_t rows = (HW_BM - 1 + a.W - 1) / a.W + 1;
-  const int64_t seps = (HW_BM - 1) / HW + 1;
   // 32-channel partitions may use both chunk areas for one wider halo image (ONECH)
-  return (rows + 2 + seps) * halo_wgrad_pitch(a.W) <= (a.C == 32 ? 2 : 1) * HW_HPX;
+  return halo_need(HW_BM, a.H, a.W, halo_wgrad_pitch(a.W)) <= (a.C == 32 ? 2 : 1) * HW_HPX;
 }
 
 // one 32-channel chunk whose halo needs the combined image
 static bool halo_wgrad_onech(const WGradArgs& a) {
-  const int64_t HW = (int64_t)a.H * a.W;
-  const int64_t rows = (HW_BM - 1 + a.W - 1) / a.W + 1;
-  const int64_t seps = (HW_BM - 1) / HW + 1;
-  return a.C == 32 && (rows + 2 + seps) * halo_wgrad_pitch(a.W) > HW_HPX;
+  return a.C == 32 && halo_need(HW_BM, a.H, a.W, halo_wgrad_pitch(a.W)) > HW_HPX;
+}
+
+// Halo DMA instructions per wave and chunk of the 4-wave linear-tile weight gradient on
+// H x W images: the smallest instantiated count (HT, see launch_halo_wgrad) that covers
+// the slots a tile reads.  Instantiated next to the pitch: 4 of 7 at pitch 16 (ResNet
+// layer3), 5 of 7 at pitch 32 (layer2).
+int conv3_halo_wgrad_dma_count(int H, int W) {
+  const int W2 = halo_wgrad_pitch(W);
+  const int64_t need = halo_need(HW_BM, H, W, W2);
+  if (need > HW_HPX) return HW_HIW;  // (ONECH / strip tiles: whole stages)
+  const int c = halo_dma_count(need, HW_HIW);
+  if (W2 == 16 && c <= 4) return 4;
+  if (W2 == 32 && c <= 5) return 5;
+  return HW_HIW;
 }
 
 int64_t conv3_halo_wgrad_ws_floats(int Kout, int Ncols) {
@@ -1900,6 +1972,15 @@ static void launch_halo_wgrad(const WGradArgs& a, const HaloWPlan& h, dim3 grid,
       else
         hipLaunchKernelGGL((conv3_halo_wgrad_kernel<0, ONECH, false, true>), grid,
                            dim3(512), 0, s, a, h);
+      return;
+    }
+  }
+  // 4-wave form: the geometry-sized halo fetch where a count is instantiated for the pitch
+  if constexpr (!ONECH && !STRIP && (W2T == 16 || W2T == 32)) {
+    constexpr int HT = W2T == 16 ? 4 : 5;
+    if (conv3_halo_wgrad_dma_count(a.H, a.W) == HT) {
+      hipLaunchKernelGGL((conv3_halo_wgrad_kernel<W2T, false, false, false, 4, HT>), grid,
+                         dim3(256), 0, s, a, h);
       return;
     }
   }
