@@ -1594,6 +1594,59 @@ void lars_step_dev(Tensor p, Tensor g, Tensor buf, Tensor shadow, Tensor step, T
                      nesterov ? 1 : 0, cur_stream());
 }
 
+// ---- weight EMA over the flat arena and over the model's floating-point buffers
+void ema_update(Tensor ema, Tensor p, Tensor step, double decay, bool warmup) {
+  CHECK_CUDA(p);
+  check_arena(p, p, "ema_update: p");
+  check_arena(ema, p, "ema_update: ema");
+  TORCH_CHECK(ema.numel() == p.numel() && p.numel() % 4 == 0,
+              "ema_update: ema and p of one length, a multiple of 4");
+  check_f32_n(step, 1, p, "ema_update: step");
+  TORCH_CHECK(decay >= 0.0 && decay < 1.0, "ema_update: decay must be in [0, 1), got ", decay);
+  const c10::OptionalDeviceGuard gd(device_of(p));
+  mpa::ema_update(ema.data_ptr<float>(), p.data_ptr<float>(), step.data_ptr<float>(), p.numel(),
+                  (float)decay, warmup ? 1 : 0, cur_stream());
+}
+
+// table: the device table the kernel reads; table_host: its host twin, which the sources are
+// checked against on every call (no device read-back)
+void ema_update_multi(Tensor ema_buf, Tensor table, Tensor table_host, std::vector<Tensor> srcs,
+                      Tensor step, double decay, bool warmup) {
+  CHECK_CUDA(ema_buf);
+  CHECK_F32(ema_buf);
+  CHECK_CONTIG(ema_buf);
+  const int64_t nbuf = (int64_t)srcs.size();
+  TORCH_CHECK(table.scalar_type() == torch::kInt64 && table.dim() == 2 &&
+                  table.size(0) == nbuf && table.size(1) == mpa::EMA_COLS &&
+                  table.is_contiguous() && table.device() == ema_buf.device() && nbuf < INT32_MAX,
+              "ema_update_multi: table [nbuf][3] int64 on ema_buf's device, one row per source");
+  TORCH_CHECK(table_host.scalar_type() == torch::kInt64 && table_host.is_cpu() &&
+                  table_host.is_contiguous() && table_host.sizes() == table.sizes(),
+              "ema_update_multi: table_host is the table's int64 CPU twin");
+  check_f32_n(step, 1, ema_buf, "ema_update_multi: step");
+  TORCH_CHECK(decay >= 0.0 && decay < 1.0, "ema_update_multi: decay must be in [0, 1), got ",
+              decay);
+  const int64_t* th = table_host.data_ptr<int64_t>();
+  for (int64_t i = 0; i < nbuf; ++i) {
+    const Tensor& t = srcs[i];
+    const int64_t* r = th + i * mpa::EMA_COLS;
+    TORCH_CHECK(t.is_cuda() && t.device() == ema_buf.device() &&
+                    t.scalar_type() == torch::kFloat32 && t.is_contiguous(),
+                "ema_update_multi: source ", i, " must be contiguous fp32 on ema_buf's device");
+    TORCH_CHECK(r[mpa::EMA_SRC] == (int64_t)reinterpret_cast<uintptr_t>(t.data_ptr()) &&
+                    r[mpa::EMA_LEN] == t.numel(),
+                "ema_update_multi: table row ", i, " does not describe source ", i,
+                " (the tensor moved or changed size: rebuild the table)");
+    TORCH_CHECK(r[mpa::EMA_OFF] >= 0 && r[mpa::EMA_OFF] <= ema_buf.numel() &&
+                    r[mpa::EMA_LEN] <= ema_buf.numel() - r[mpa::EMA_OFF],
+                "ema_update_multi: table row ", i, " lies outside ema_buf");
+  }
+  const c10::OptionalDeviceGuard gd(device_of(ema_buf));
+  mpa::ema_update_multi(ema_buf.data_ptr<float>(), ema_buf.numel(), table.data_ptr<int64_t>(),
+                        (int)nbuf, step.data_ptr<float>(), (float)decay, warmup ? 1 : 0,
+                        cur_stream());
+}
+
 void transpose_krsc(Tensor w, Tensor wt, Tensor seg, int64_t total_tiles,
                     c10::optional<Tensor> step_inc) {
   CHECK_CUDA(w);
@@ -2088,6 +2141,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("trust_ratio", &trust_ratio, "per-segment norms and trust ratio from the partials");
   m.def("lamb_step_dev", &lamb_step_dev, "LAMB stage 2 / AdamW on the segment plan");
   m.def("lars_step_dev", &lars_step_dev, "LARS on the segment plan");
+  m.def("ema_update", &ema_update, "ema += (1 - d_t) * (p - ema) over a flat fp32 arena");
+  m.def("ema_update_multi", &ema_update_multi,
+        "the same update for a table of small fp32 tensors, one launch");
   m.def("transpose_krsc", &transpose_krsc, py::arg("w"), py::arg("wt"), py::arg("seg"),
         py::arg("total_tiles"), py::arg("step_inc") = py::none());
   m.def("zero_f32", &zero_f32, "t.zero_() on the native path");

@@ -486,6 +486,17 @@ void lars_step_dev(float* p, const float* g, float* buf, bf16_raw* shadow, int64
                    const float* step, const float* hyper, const int64_t* seg,
                    const int* chunk_seg, int nseg, int nchunks, const float* ratio,
                    float momentum, float dampening, float wd, int nesterov, hipStream_t s);
+// Weight EMA: ema[i] += w * (p[i] - ema[i]) for i in [0, n) (n % 4 == 0, 16-B aligned),
+// w = 1 - d_t, d_t = warmup ? min(decay, (1 + t) / (10 + t)) : decay, t = step[0]; every
+// operation rounded on its own in fp32.  Reads p, writes only ema[0:n).
+void ema_update(float* ema, const float* p, const float* step, int64_t n, float decay,
+                int warmup, hipStream_t s);
+// The same update for nbuf small fp32 tensors in one launch.  table [nbuf][EMA_COLS] int64
+// on the device = (source address, offset into ema_buf, length); sources need 4-byte
+// alignment only; n: elements of ema_buf (a row outside it is not followed).
+enum { EMA_SRC = 0, EMA_OFF = 1, EMA_LEN = 2, EMA_COLS = 3 };
+void ema_update_multi(float* ema_buf, int64_t n, const int64_t* table, int nbuf,
+                      const float* step, float decay, int warmup, hipStream_t s);
 // wt[c][t][k] = w[k][t][c] per segment (src_off, dst_off, K, RS, C, first_tile) of seg
 // step_inc (optional): the optimizer's step counter, incremented by the same launch
 void transpose_krsc(const bf16_raw* w, bf16_raw* wt, const int64_t* seg, int nseg,

@@ -25,6 +25,10 @@ from typing import Any, Dict, Optional, Tuple
 
 import torch
 
+from .utils.logging import get_logger
+
+EMA_KEY = "ema_state_dict"
+
 
 def checkpoint_path(checkpoint_dir: str, model_name: str) -> str:
     return os.path.join(checkpoint_dir, "checkpoint_{}.pt".format(model_name))
@@ -58,9 +62,13 @@ def save_checkpoint(state: Dict[str, Any], epoch: int, model_name: str, checkpoi
 
 
 def load_checkpoint(checkpoint_fpath: str, model, optimizer=None,
-                    map_location="cpu") -> Tuple[Any, Any, int]:
+                    map_location="cpu", ema=None) -> Tuple[Any, Any, int]:
     """Restore model (+ optimizer) and return ``(model, optimizer, epoch)`` like
-    ``helpers.load_checkpoint``.  The flat-arena bf16 weight shadow is refreshed."""
+    ``helpers.load_checkpoint``.  The flat-arena bf16 weight shadow is refreshed.
+
+    ``ema`` (a ``ModelEMA``): restored from the checkpoint's ``ema_state_dict``; a checkpoint
+    without one starts the average from the loaded weights, and one log line says so.  (The
+    number of updates the warm-up counts is the optimizer's ``mpa_step``.)"""
     ck = torch.load(checkpoint_fpath, map_location=map_location, weights_only=True)
     model.load_state_dict(ck["state_dict"])
     arena = getattr(model, "_mpa_arena", None)
@@ -68,6 +76,13 @@ def load_checkpoint(checkpoint_fpath: str, model, optimizer=None,
         arena.sync_shadow()
     if optimizer is not None and "optimizer" in ck:
         optimizer.load_state_dict(ck["optimizer"])
+    if ema is not None:
+        if EMA_KEY in ck:
+            ema.load_state_dict(ck[EMA_KEY])
+        else:
+            ema.reset()
+            get_logger().info("_Checkpoint has no {}: the weight EMA starts from the loaded "
+                              "weights".format(EMA_KEY))
     return model, optimizer, int(ck.get("epoch", 0))
 
 
@@ -75,7 +90,12 @@ def read_checkpoint(path: str) -> Dict[str, Any]:
     return torch.load(path, map_location="cpu", weights_only=True)
 
 
-def build_state(epoch: int, model, optimizer, loss: float) -> Dict[str, Any]:
-    """The payload of ``main.py:163-168``."""
-    return {"epoch": epoch, "state_dict": model.state_dict(),
-            "optimizer": optimizer.state_dict(), "loss": loss}
+def build_state(epoch: int, model, optimizer, loss: float, ema=None) -> Dict[str, Any]:
+    """The payload of ``main.py:163-168``; with a weight EMA two more keys: the averaged
+    model's ``ema_state_dict`` and ``ema`` = its settings (plain Python types)."""
+    state = {"epoch": epoch, "state_dict": model.state_dict(),
+             "optimizer": optimizer.state_dict(), "loss": loss}
+    if ema is not None:
+        state[EMA_KEY] = ema.state_dict()
+        state["ema"] = {"decay": float(ema.decay), "warmup": bool(ema.warmup)}
+    return state

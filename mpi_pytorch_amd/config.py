@@ -84,6 +84,10 @@ class Config:
     cutmix_alpha: float = 0.0              # CutMix: the pasted rectangle's area from Beta(alpha, alpha)
     mix_prob: float = 1.0                  # probability that a sample is mixed at all
     mix_switch_prob: float = 0.5           # both on: probability of CutMix (else Mixup)
+    # exponential moving average of the weights on the device (ema.py; off at 0)
+    ema_decay: float = 0.0                 # in [0, 1): ema += (1 - d_t) * (p - ema) after each update
+    ema_warmup: bool = True                # d_t = min(ema_decay, (1 + t) / (10 + t))
+    eval_ema: bool = False                 # evaluation pipeline: load the checkpoint's averaged weights
     bucket_mb: float = 16.0                # gradient all-reduce bucket size (MiB)
     grad_comm_dtype: str = "fp32"          # fp32 | bf16 (wire dtype of the gradient all-reduce)
     overlap_comm: bool = True              # launch bucket all-reduce during backward
@@ -140,6 +144,8 @@ class Config:
             raise ValueError("mixup_alpha and cutmix_alpha must be >= 0 (0 = off)")
         if not (0.0 <= self.mix_prob <= 1.0 and 0.0 <= self.mix_switch_prob <= 1.0):
             raise ValueError("mix_prob and mix_switch_prob must be in [0, 1]")
+        if not 0.0 <= self.ema_decay < 1.0:
+            raise ValueError("ema_decay must be in [0, 1) (0 = off)")
         if self.eval_topk < 0:
             raise ValueError("eval_topk must be >= 0 (0 or 1 = top-1 only)")
 

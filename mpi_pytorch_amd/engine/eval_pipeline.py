@@ -39,7 +39,7 @@ import numpy as np
 import torch
 
 from ..config import Config
-from ..checkpoint import read_checkpoint
+from ..checkpoint import read_checkpoint, EMA_KEY
 from ..data.loader import IMAGENET_MEAN, IMAGENET_STD
 from ..data.manifest import SyntheticImages, FolderImages, images_available, synthetic_manifest
 from ..models import initialize_model, input_spec
@@ -50,13 +50,20 @@ from ..utils.logging import init_logger
 
 def load_predictor(cfg: Config, device, ckpt_path: Optional[str] = None):
     """``initialize_model(..., use_pretrained=False)`` + checkpoint ``state_dict``
-    (evaluation_pipeline.py:138-147)."""
+    (evaluation_pipeline.py:138-147).  ``cfg.eval_ema``: the checkpoint's averaged weights
+    (``ema_state_dict``, written by a run with ``ema_decay`` > 0) instead."""
     model, _ = initialize_model(cfg.MODEL_NAME, cfg.NUM_CLASSES, False, use_pretrained=False)
     model = model.to(device)
     model._mpa_arena = ParamArena(model, device)
     path = ckpt_path or os.path.join(cfg.CHECKPOINT_DIR, "checkpoint_{}.pt".format(cfg.MODEL_NAME))
+    if cfg.eval_ema and not os.path.exists(path):
+        raise FileNotFoundError("eval_ema: no checkpoint at {}".format(path))
     if os.path.exists(path):
-        sd = read_checkpoint(path)["state_dict"]
+        ck = read_checkpoint(path)
+        if cfg.eval_ema and EMA_KEY not in ck:
+            raise KeyError("eval_ema: checkpoint {} has no {} (it was written by a run without "
+                           "ema_decay); evaluate it without --eval_ema".format(path, EMA_KEY))
+        sd = ck[EMA_KEY if cfg.eval_ema else "state_dict"]
         model.load_state_dict(sd)
         model._mpa_arena.sync_shadow()
     model.eval()

@@ -29,6 +29,7 @@ import torch.nn as nn
 from ..models import initialize_model, InceptionOutputs
 from ..ops import functional as Fn
 from ..optim import build_optimizer
+from ..ema import ModelEMA
 from ..parallel import ParamArena, GradBucketer, sync_params, World, agree_tuned_tiles
 
 
@@ -195,9 +196,13 @@ class StepTimer:
 
 
 class TrainStep:
-    def __init__(self, model: nn.Module, optimizer, world: World, label_smoothing: float = 0.0):
+    def __init__(self, model: nn.Module, optimizer, world: World, label_smoothing: float = 0.0,
+                 ema: Optional[ModelEMA] = None):
         self.model = model
         self.opt = optimizer
+        # weight EMA (ema.py): updated right after the optimizer, inside the "opt" phase -
+        # and so inside a captured graph; None = off, the step launches what it always did
+        self.ema = ema
         self.world = world
         self.label_smoothing = float(label_smoothing)  # a host constant: graph-capture safe
         self.arena: ParamArena = model._mpa_arena
@@ -280,6 +285,8 @@ class TrainStep:
             m.range_pop()
             m.range_push("opt")
         self.opt.step()
+        if self.ema is not None:
+            self.ema.update()
         if t is not None:
             t.mark(4)
         if m is not None:
@@ -323,11 +330,14 @@ class TrainStep:
     def _training_state(self):
         """Everything a training step mutates besides the (per-step zeroed) gradients:
         master / bf16 / transposed weights, optimizer moments and step counter, BN running
-        statistics and batch counts, the running loss sum, the dropout stream position."""
+        statistics and batch counts, the running loss sum, the dropout stream position, the
+        weight EMA."""
         a = self.arena
         dev = [t for t in (a.master, a.shadow, a.shadow_t, self.loss_sum) if t is not None]
         dev += [v for v in vars(self.opt).values() if torch.is_tensor(v)]
         dev += list(self.model.buffers())
+        if self.ema is not None:
+            dev += [self.ema.ema, self.ema.ema_buf]
         bns = [m for m in self.model.modules() if hasattr(m, "_batches_host")]
         return dev, bns
 
@@ -406,12 +416,13 @@ def build_training(name: str, num_classes: int, device, world: World, lr: float,
                    comm_dtype: str = "fp32", comm_ctas: Optional[int] = None,
                    schedule: Optional[dict] = None, clip_grad_norm: float = 0.0,
                    label_smoothing: float = 0.0, trust_coef: float = 0.001,
-                   wd_exclude_1d: bool = True):
+                   wd_exclude_1d: bool = True, ema_decay: float = 0.0, ema_warmup: bool = True):
     """``schedule``: keyword arguments of ``optim.set_schedule`` (None: constant LR);
     ``clip_grad_norm`` > 0: global-norm gradient clipping (``optim.set_clip``);
     ``label_smoothing``: the training loss's label smoothing in [0, 1];
     ``trust_coef`` / ``wd_exclude_1d``: the layer-wise optimizers' settings (adamw | lamb |
-    lars only)."""
+    lars only); ``ema_decay`` > 0: a weight EMA (``ema.ModelEMA``) as ``step.ema``, started
+    from the synced weights (``ema_warmup``: ``min(decay, (1 + t) / (10 + t))``)."""
     model, input_size = build_model(name, num_classes, feature_extract, device, world,
                                     bucket_mb=bucket_mb, overlap=overlap, comm_dtype=comm_dtype,
                                     comm_ctas=comm_ctas)
@@ -423,4 +434,7 @@ def build_training(name: str, num_classes: int, device, world: World, lr: float,
         opt.set_clip(clip_grad_norm)
     sync_params(model)
     model.train()
-    return model, opt, TrainStep(model, opt, world, label_smoothing), input_size
+    if not 0.0 <= ema_decay < 1.0:
+        raise ValueError("ema_decay must be in [0, 1) (0 = off)")
+    ema = ModelEMA(model, opt, ema_decay, ema_warmup) if ema_decay > 0.0 else None
+    return model, opt, TrainStep(model, opt, world, label_smoothing, ema), input_size

@@ -257,7 +257,7 @@ def run_training(cfg: Config) -> dict:
         cfg.grad_comm_dtype, None if cfg.grad_comm_ctas < 0 else cfg.grad_comm_ctas,
         schedule=schedule, clip_grad_norm=cfg.clip_grad_norm,
         label_smoothing=cfg.label_smoothing, trust_coef=cfg.trust_coef,
-        wd_exclude_1d=cfg.wd_exclude_1d)
+        wd_exclude_1d=cfg.wd_exclude_1d, ema_decay=cfg.ema_decay, ema_warmup=cfg.ema_warmup)
     log.info("_Model Created: {}".format(cfg.MODEL_NAME))
     spec = input_spec(model, out_hw)
     for ld in (train_loader, val_loader):
@@ -268,11 +268,16 @@ def run_training(cfg: Config) -> dict:
     ckpt = os.path.join(cfg.CHECKPOINT_DIR, cfg.CHECKPOINT_NAME)
     if cfg.FROM_CHECKPOINT:
         log.info("_Loading Checkpoint")
-        _m, _o, saved_epoch = load_checkpoint(ckpt, model, opt, map_location="cpu")
+        # (every rank reads the same file, so the restored weight EMA - or, without an
+        # ema_state_dict, the one started from the loaded weights - is equal on every rank)
+        _m, _o, saved_epoch = load_checkpoint(ckpt, model, opt, map_location="cpu",
+                                              ema=step.ema)
         start_epoch = saved_epoch + 1 if cfg.resume_epoch else 0
         log.info("_Checkpoint loaded")
     from ..parallel import sync_params
     sync_params(model)
+    if step.ema is not None and not cfg.FROM_CHECKPOINT:
+        step.ema.reset()  # the average starts from the synced weights
     # the reference's exact string (main.py:133 logs "CPU" whatever the device); the
     # actual compute device goes on a line of its own
     log.info("_Model loaded to CPU")
@@ -347,8 +352,8 @@ def run_training(cfg: Config) -> dict:
         dog.pause()
         if rank == 0:
             log.info("_Creating a checkpoint at epoch {}".format(epoch))
-            save_checkpoint(build_state(epoch, model, opt, tr_loss), epoch, cfg.MODEL_NAME,
-                            cfg.CHECKPOINT_DIR, cfg.MODELS_DIR)
+            save_checkpoint(build_state(epoch, model, opt, tr_loss, step.ema), epoch,
+                            cfg.MODEL_NAME, cfg.CHECKPOINT_DIR, cfg.MODELS_DIR)
             log.info("_Checkpoint saved")
             if val_loader is not None:
                 log.info("_Evaluating model")
@@ -359,6 +364,14 @@ def run_training(cfg: Config) -> dict:
                 if topk:
                     rec["acc_top{}".format(topk)] = acc_k
                     log.info("_Epoch: {} | Top-{} Acc: {}".format(epoch, topk, acc_k))
+                if step.ema is not None:  # a second pass over the averaged model
+                    with step.ema.swapped_in():
+                        acc, acc_k = _evaluate(model, val_loader, topk)
+                    rec["acc_ema"] = acc
+                    log.info("_Epoch: {} | EMA Acc: {}".format(epoch, acc))
+                    if topk:
+                        rec["acc_ema_top{}".format(topk)] = acc_k
+                        log.info("_Epoch: {} | EMA Top-{} Acc: {}".format(epoch, topk, acc_k))
         metrics.write(**rec)
         history.append(rec)
         if size > 1:

@@ -726,6 +726,51 @@ def sgd_step_dev(master, grad, buf, shadow, step_t, hyper, momentum, dampening, 
              nesterov, float(hyper[HYPER_SCALE]))
 
 
+# ---- weight EMA; csrc/kernels/optim.hip
+EMA_SRC, EMA_OFF, EMA_LEN = range(3)
+EMA_COLS = 3
+
+
+def ema_weight(step_t, decay, warmup):
+    """fp32 mirror of the kernels' ``w = 1 - d_t``, ``d_t = min(decay, (1 + t) / (10 + t))``
+    with warm-up (``t = step_t``, the updates completed), else ``decay``."""
+    f = np.float32
+    d = f(decay)
+    if warmup:
+        t = f(float(step_t.item()))
+        d = min(d, (f(1) + t) / (f(10) + t))
+    return f(1) - d
+
+
+def _ema_into(ema, p, w):
+    diff = p - ema       # three separately rounded fp32 tensor ops, like ema_elem
+    prod = diff * float(w)
+    ema.add_(prod)
+
+
+def ema_update(ema, p, step_t, decay, warmup):
+    """ema += w * (p - ema) over a flat fp32 arena; bit for bit the kernel."""
+    if not 0.0 <= decay < 1.0:
+        raise ValueError("ema_update: decay must be in [0, 1), got %r" % (decay,))
+    _ema_into(ema, p, ema_weight(step_t, decay, warmup))
+
+
+def ema_update_multi(ema_buf, table, table_host, srcs, step_t, decay, warmup):
+    """The same update for the small fp32 tensors ``srcs``: source ``i`` averages into
+    ``ema_buf[off:off + len]`` of row ``i`` of ``table_host`` [nbuf][EMA_COLS] int64 =
+    (source address, offset, length).  ``table`` is the kernel's device copy."""
+    if not 0.0 <= decay < 1.0:
+        raise ValueError("ema_update_multi: decay must be in [0, 1), got %r" % (decay,))
+    rows = table_host.tolist()
+    if len(rows) != len(srcs):
+        raise ValueError("ema_update_multi: one table row per source")
+    w = ema_weight(step_t, decay, warmup)
+    for (_addr, off, ln), s in zip(rows, srcs):
+        if ln != s.numel() or off < 0 or off + ln > ema_buf.numel():
+            raise ValueError("ema_update_multi: a table row does not describe its source")
+        _ema_into(ema_buf[off:off + ln], s.reshape(-1), w)
+
+
 # ---- layer-wise optimizers on the segment plan (AdamW / LAMB / LARS); csrc/kernels/optim.hip
 # seg [nseg][SEG_COLS] int64 rows (csrc/kernels/api.h SEG_*); the segments tile [0, n)
 SEG_OFF, SEG_LEN, SEG_FIRST, SEG_NCHUNK, SEG_FLAGS = range(5)

@@ -12,7 +12,11 @@ and ``lars`` on the segment plan of the ResNet-18 headline arena (64,500 classes
 process: AdamW moves Adam's 30 bytes per parameter, LAMB 46 (stage 1 reads p, g, m, v again),
 LARS 30 against SGD-momentum's 22 (two norm passes).
 
-    python tools/adam_probe.py [--recipe | --layerwise]
+With ``--ema`` the weight EMA's kernels ``ema_update`` (12 bytes per parameter) and
+``ema_update_multi`` (the BN running statistics, one launch) beside ``adam`` on the same
+arena, in one process.
+
+    python tools/adam_probe.py [--recipe | --layerwise | --ema]
 """
 import sys
 
@@ -93,9 +97,59 @@ def layerwise(k, dev, flush):
                   f"(min {lo:.1f}, max {hi:.1f})  {bpp * n / us / 1e6:6.2f} TB/s", flush=True)
 
 
+def ema(k, dev, flush):
+    """The weight EMA's two kernels beside ``adam`` on the ResNet-18 headline arena:
+    ``ema_update`` moves 12 bytes per parameter (p read, ema read and written),
+    ``ema_update_multi`` the same per element of the model's 40 BN running statistics."""
+    from mpi_pytorch_amd.models import initialize_model
+    from mpi_pytorch_amd.parallel.arena import ParamArena, _align
+    model = initialize_model("resnet18", 64500, False, False)[0]
+    n = ParamArena(model, torch.device("cpu"), shadow=False).n_train
+    bufs = [torch.randn(b.numel(), device=dev) for b in model.buffers() if b.is_floating_point()]
+    rows, off = [], 0
+    for b in bufs:
+        rows.append([b.data_ptr(), off, b.numel()])
+        off += _align(b.numel())
+    table_host = torch.tensor(rows, dtype=torch.int64)
+    table = table_host.to(dev)
+    ema_buf = torch.zeros(off, device=dev)
+    nb = sum(b.numel() for b in bufs)
+    print("resnet18 / 64,500 classes: %d elements, %d float buffers of %d elements"
+          % (n, len(bufs), nb), flush=True)
+    p = torch.randn(n, device=dev)
+    e = torch.randn(n, device=dev)
+    g = torch.randn(n, device=dev) * 1e-2
+    m = torch.zeros(n, device=dev)
+    v = torch.zeros(n, device=dev)
+    sh = torch.empty(n, dtype=torch.bfloat16, device=dev)
+    st = torch.ones(1, device=dev)
+
+    def adam():
+        k.adam_step(p, g, m, v, sh, st, 1e-3, 0.9, 0.999, 1e-8, 0.0, 1.0)
+
+    def ema_update():
+        k.ema_update(e, p, st, 0.9998, True)
+
+    def ema_multi():
+        k.ema_update_multi(ema_buf, table, table_host, bufs, st, 0.9998, True)
+
+    # (adam and ema_update run twice: the spread between equal runs is the yardstick)
+    runs = [("adam", adam, 30 * n), ("ema_update", ema_update, 12 * n),
+            ("ema_update_multi", ema_multi, 12 * nb), ("adam", adam, 30 * n),
+            ("ema_update", ema_update, 12 * n)]
+    for cold in (False, True):
+        for name, fn, nbytes in runs:
+            us, lo, hi = _time(fn, flush, cold)
+            print(f"{name:17s} n={n / 1e6:7.2f}M {'cold' if cold else 'warm'}: {us:8.1f} us "
+                  f"(min {lo:.1f}, max {hi:.1f})  {nbytes / us / 1e6:6.3f} TB/s", flush=True)
+
+
 def main():
     recipe = "--recipe" in sys.argv[1:]
     k = _ext.load()
+    if "--ema" in sys.argv[1:]:
+        dev = torch.device("cuda:0")
+        return ema(k, dev, torch.empty(1 << 30, dtype=torch.float32, device=dev))
     if "--layerwise" in sys.argv[1:]:
         dev = torch.device("cuda:0")
         return layerwise(k, dev, torch.empty(1 << 30, dtype=torch.float32, device=dev))
