@@ -39,32 +39,16 @@
 //    block's tiles and are written once per block.
 #include <algorithm>
 #include <atomic>
+#include <cstdio>
 #include <cstdlib>
 #include <type_traits>
 #include "igemm_common.h"
+#include "halo_plan.h"
 
 namespace mpa {
 
-constexpr int HB_BM = 256, HB_BN = 64, HB_NW = 4;
-constexpr int HB_HIW = 9;                       // halo DMA instructions per wave per chunk
-constexpr int HB_HPX = 16 * HB_NW * HB_HIW;     // 576 halo pixels per chunk
-constexpr int HB_HBYTES = HB_HPX * 64;          // 36 KiB
-constexpr int HB_WIW = 9;                       // weight DMA instructions per wave per chunk
-constexpr int HB_WBYTES = 9 * HB_BN * 64;       // 36 KiB: [tap][64 cols][32 k]
-constexpr int HB_RED = HB_NW * HB_BN * 2 * 4;   // epilogue cross-wave statistics
-constexpr int HB_COLS = 4 * HB_BN * 4;          // per-column epilogue operands [4][64]
-constexpr int HB_LDS = 2 * HB_HBYTES + 2 * HB_WBYTES + HB_RED + HB_COLS;  // 150,528 B
-
-struct HaloPlan {
-  int w2;               // halo row pitch P: W + 1 (one shared zero column) rounded up to 8
-  int btoff[9];         // tap t = (dh + 1) * 3 + (dw + 1): byte offset bt * aC * 2 of its
-                        // weight row segment (the host orders any 3x3 tap table this way)
-  uint32_t mag_w, mag_w2, mag_h1, mag_hw;  // floor(2^32 / d) + 1: exact n / d for n*d < 2^32
-  int tiles_m, tiles_total, cc;
-  uint32_t a_bytes, b_bytes;
-  int hiw;              // (256-pixel tiles) halo DMA instructions per producer wave and item:
-                        // the slots any tile of this geometry reads (halo_need), <= HB_HIW
-};
+// (tile constants HB_* / HW_*, the plan structs HaloPlan / StripPlan / HaloWPlan and the
+// EP_* flavour bits: halo_plan.h, with the host planner that fills them)
 
 // Zero an LDS range (16-B aligned, a multiple of 16 B) with the whole block; no barrier.
 // The halo stages are zeroed once per block: with a geometry-sized fetch (HaloPlan::hiw,
@@ -78,9 +62,6 @@ __device__ __forceinline__ void lds_zero(char* lds, int bytes, int tid, int nthr
 __device__ __forceinline__ bf16x8 frag16(const char* lds_byte) {
   return __builtin_bit_cast(bf16x8, *LDS_PTR(const u32x4, lds_byte));
 }
-
-// Epilogue flavours (compile-time, so the fused epilogue below is one straight-line block)
-enum : int { EP_RELU = 1, EP_BETA = 2, EP_BNRED = 4, EP_STATS = 8, EP_BIAS = 16 };
 
 // Per-tile operands the epilogue reads from memory (accumulate: the old output; fused
 // BN-backward reduction: z, whose ReLU mask is recomputed like bn_fwd_train rounded y, so
@@ -795,18 +776,6 @@ __global__ __launch_bounds__(MI == 4 ? 512 : 256, 1) void conv3_halo_kernel(IGem
 //  (tools/dma_probe.hip).
 //  Producer waves only (8-wave blocks), 64-wide column tiles (N % 64 == 0).
 // ======================================================================================
-struct StripPlan {
-  int tr, tw, p;            // tile rows / columns, LDS pitch (pixels)
-  int hiw;                  // halo DMA instructions per producer wave per item (<= 9)
-  int tiles_c, tiles_img;   // column strips per row band, tiles per image
-  int tiles_total, cc;
-  uint32_t mag_tw, mag_p, mag_tc, mag_timg;  // floor(2^32 / d) + 1 (0: d == 1)
-  int btoff[9];
-  uint32_t a_bytes, b_bytes;
-  int ch, cw;               // tap-set centre shift: output (i, j) reads input rows / cols
-                            // i + ch - 1 .. i + ch + 1 (same conv 0, valid 1, its dgrad -1)
-};
-
 // n / d from udiv's magic, with magic 0 standing for d == 1 (floor(2^32 / 1) + 1 wraps)
 __device__ __forceinline__ uint32_t udiv1(uint32_t n, uint32_t mag) {
   return mag ? udiv(n, mag) : n;
@@ -1115,31 +1084,6 @@ __global__ __launch_bounds__(512, 1) void conv3_strip_kernel(IGemmArgs p, StripP
 //  all 64 k and 9 taps: 36 accumulators of 16x16.  Partials go to a [Z][K][9C] slab
 //  (Z = blocks per partition), summed into the fp32 gradient arena by wgrad_reduce.
 // ======================================================================================
-constexpr int HW_BM = 128;                    // pixels per tile
-constexpr int HW_HIW = 7;                     // halo DMA instructions per wave per chunk
-constexpr int HW_HPX = 16 * 4 * HW_HIW;       // 448 halo pixels
-constexpr int HW_HBYTES = HW_HPX * 64;        // 28 KiB per chunk
-constexpr int HW_DBYTES = HW_BM * 64 * 2;     // 16 KiB: dy tile, 4 k-steps x [32 px][64 k]
-constexpr int HW_STAGE = HW_DBYTES + 2 * HW_HBYTES;  // 72 KiB
-constexpr int HW_LDS = 2 * HW_STAGE;                 // 147,456 B
-
-struct HaloWPlan {
-  int toff[9];
-  int w2;  // halo row pitch in pixels: W + 2 rounded up to 16 (see the B-address note)
-  uint32_t mag_w, mag_w2, mag_h1, mag_hw;
-  int tiles_m, parts, kparts, Z;
-  uint32_t dy_bytes, x_bytes;
-  // STRIP: tiles of tr rows x tw columns of one image (w2 = tw + 2 rounded up to 16), for
-  // images too wide for the 128-pixel linear tiles' halo (VGG 224^2 / 112^2)
-  int tr, tw, tiles_c, tiles_img;
-  uint32_t mag_tw, mag_tc, mag_timg;  // (0: divisor 1)
-  // XCD-grouped block order (grid % 8 == 0): logical block L = xcd * (grid / 8) + slot, so
-  // one XCD's blocks are consecutive (z, part) ids - they share z lanes and cover a run of
-  // partitions, and each staged dy / x tile is read into that XCD's L2 by the blocks that
-  // consume it, instead of every XCD fetching every x (or dy) panel
-  int xmap;
-};
-
 // W2T: the halo pitch as a compile-time constant (16 / 32 / 48 / 64: every ResNet and
 // Inception size), so a tap's row offset is an immediate DS offset; 0 = runtime pitch.
 // ONECH (C == 32, images too wide for a 448-pixel halo, e.g. Inception's 147 x 147
@@ -1492,14 +1436,26 @@ __global__ __launch_bounds__(PROD ? 512 : 256, 1) void conv3_halo_wgrad_kernel(W
 }
 
 // ------------------------------------------------------------------------------ host
-static bool g_halo = [] {
-  const char* e = getenv("MPA_HALO");
-  return !(e && e[0] == '0');
+// Every decision - whether the engine takes a launch, which instance runs it, its grid and
+// its plan struct - is plan_halo / plan_halo_wgrad of halo_plan.h.  Here: the process's
+// switches, the CU count, and one switch per kernel family from a plan to its instance.
+static HaloSwitches g_sw = [] {
+  HaloSwitches sw;
+  if (const char* e = getenv("MPA_HALO")) sw.halo = e[0] != '0';
+  if (const char* e = getenv("MPA_HALO_WRES")) sw.wres = atoi(e) != 0;
+  if (const char* e = getenv("MPA_HALO_STRIP")) sw.strip = atoi(e);
+  if (const char* e = getenv("MPA_HALO_MI7")) sw.mi7 = atoi(e) != 0;
+  if (const char* e = getenv("MPA_HALO_WXMAP")) sw.wxmap = e[0] != '0';
+  if (const char* e = getenv("MPA_HALO_WPROD")) sw.wprod = e[0] != '0';
+  return sw;
 }();
-void igemm_set_halo(int on) { g_halo = on != 0; }
-bool igemm_halo_enabled() { return g_halo; }
-
-static uint32_t magic(uint32_t d) { return (uint32_t)((1ull << 32) / d + 1); }
+void igemm_set_halo(int on) { g_sw.halo = on != 0; }
+bool igemm_halo_enabled() { return g_sw.halo; }
+void igemm_set_halo_strip(int mode) { g_sw.strip = mode; }
+void igemm_set_halo_mi7(int on) { g_sw.mi7 = on != 0; }
+void igemm_set_halo_trim(int on) { g_sw.trim = on != 0; }
+void igemm_set_halo_wprod(int on) { g_sw.wprod = on != 0; }
+void igemm_set_halo_wxmap(int on) { g_sw.wxmap = on != 0; }
 
 static int num_cus() {
   static int n = [] {
@@ -1526,512 +1482,111 @@ int active_cus() {
   return std::max(8, (n - r) / 8 * 8);
 }
 
-// halo row pitch: W pixels + one zero column shared by consecutive rows (a row's right
-// border is the next row's left border), rounded up to 8 pixels
-static int halo_pitch(int W) { return (W + 1 + 7) / 8 * 8; }
-
-// Halo slots (pixels of pitch-P rows) that the taps of any linear tile of BM pixels reach:
-// the rows the tile touches, 2 halo rows and the image separators it crosses (+1: with
-// P == W + 1 the last slot's right border is the next pixel).  One expression for the
-// admission checks (the stage must hold it) and for the geometry-sized fetch (nothing at
-// or past it is read: tools/halo_index_check.py proves that for every tile).
-static int64_t halo_need(int BM, int H, int W, int P) {
-  const int64_t HW = (int64_t)H * W;
-  const int64_t rows = (BM - 1 + W - 1) / W + 1;
-  const int64_t seps = (BM - 1) / HW + 1;
-  return (rows + 2 + seps) * P + (P == W + 1 ? 1 : 0);
-}
-
-// Geometry-sized halo fetch (A/B and tests; off: every launch fetches the whole stage)
-static bool g_halo_trim = true;
-void igemm_set_halo_trim(int on) { g_halo_trim = on != 0; }
-
-// 16-slot DMA instructions per wave (4 DMA waves, slot blocks dealt round-robin) that
-// cover `need` slots, at most the stage's hiw_max
-static int halo_dma_count(int64_t need, int hiw_max) {
-  if (!g_halo_trim) return hiw_max;
-  const int64_t blocks = (need + 15) / 16;
-  return (int)std::min<int64_t>(hiw_max, (blocks + 3) / 4);
-}
-
 // the 256-pixel linear tiles' count for an H x W image (HaloPlan::hiw)
 int conv3_halo_dma_count(int H, int W) {
-  return halo_dma_count(halo_need(HB_BM, H, W, halo_pitch(W)), HB_HIW);
+  return halo_dma_count(halo_need(HB_BM, H, W, halo_pitch(W)), HB_HIW, g_sw.trim);
 }
-
-// epilogue flavour of a launch; -1: not instantiated (the implicit GEMM runs it)
-static int halo_epi(const IGemmArgs& a) {
-  int e = 0;
-  // fused BN reduction: the z-mask form only (y is never read; see EpiIn)
-  if (a.ep_bnred)
-    return (a.beta || a.relu || a.bias || a.ep_y || !a.ep_gamma || !a.ep_beta || !a.ep_mean ||
-            !a.ep_rstd)
-               ? -1
-               : EP_BNRED;
-  if (a.relu) e |= EP_RELU;
-  if (a.beta) e |= EP_BETA;
-  if (a.stats) e |= EP_STATS;
-  if (a.bias) e |= EP_BIAS;
-  switch (e) {
-    case 0: case EP_BETA: case EP_STATS: case EP_BIAS | EP_RELU: case EP_BIAS | EP_STATS:
-      return e;
-    default:
-      return -1;
-  }
-}
-
-// eligibility of the halo engine (either tiling); `linear`: the 256-pixel linear tiles fit
-// centre shift (ch, cw) of a 3x3 stride-1 tap set: the taps Oh + dh cover ch-1 .. ch+1 (same
-// conv 0; valid conv 1; the valid conv's dgrad, padding 2, -1) and the output is the input
-// less 2*ch rows / 2*cw columns
-static bool tap_shift(const IGemmArgs& a, int& ch, int& cw) {
-  int mh = 1 << 20, mw = 1 << 20;
-  for (int t = 0; t < 9; ++t) {
-    mh = std::min(mh, a.Oh + a.taps.dh[t]);
-    mw = std::min(mw, a.Ow + a.taps.dw[t]);
-  }
-  ch = mh + 1;
-  cw = mw + 1;
-  if (ch < -1 || ch > 1 || cw < -1 || cw > 1) return false;
-  int seen = 0;  // every relative (dh, dw) in {-1,0,1}^2 exactly once
-  for (int t = 0; t < 9; ++t) {
-    const int dh = a.Oh + a.taps.dh[t] - ch, dw = a.Ow + a.taps.dw[t] - cw;
-    if (dh < -1 || dh > 1 || dw < -1 || dw > 1) return false;
-    seen |= 1 << ((dh + 1) * 3 + dw + 1);
-  }
-  return seen == 511 && a.oH == a.aH - 2 * ch && a.oW == a.aW - 2 * cw;
-}
-
-static bool halo_ok_impl(const IGemmArgs& a, bool& linear) {
-  linear = false;
-  if (!g_halo || a.nphase > 0 || a.stap || a.T != 9 || a.Uh != 1 || a.Uw != 1) return false;
-  if (a.aC % 32 != 0 || a.M <= 0 || a.oH <= 0 || a.oW <= 0) return false;
-  // 64-wide column tiles, or one 32-wide tile (DenseNet's growth-rate convs, Inception's
-  // Conv2d_2a) in the flavours instantiated for it (strip tiles: also accumulate / BN link)
-  const int e32 = halo_epi(a);
-  const bool n32_lin = a.N == 32 && (e32 == 0 || e32 == EP_STATS);
-  if (a.N % HB_BN != 0 && !(a.N == 32 && (n32_lin || e32 == EP_BETA || e32 == EP_BNRED)))
-    return false;
-  // dense [M][ldc] output (stride-1 geometry), 32-bit element offsets in the epilogue
-  if (a.dH != a.oH || a.dW != a.oW || a.Uoh != 1 || a.Uow != 1 || a.Poh != 0 || a.Pow != 0)
-    return false;
-  if ((int64_t)a.M * a.ldc >= (1ll << 31) || a.ldc < a.N) return false;
-  if (halo_epi(a) < 0) return false;  // an epilogue flavour without an instantiation
-  if (a.Ktot != 9 * a.aC) return false;
-  int ch, cw;
-  if (!tap_shift(a, ch, cw)) return false;
-  const int64_t HW = (int64_t)a.aH * a.aW, OHW = (int64_t)a.oH * a.oW;
-  if (a.M % OHW != 0) return false;
-  if ((int64_t)(a.M / OHW) * HW * a.aC * 2 >= (1ll << 31)) return false;
-  if ((int64_t)a.N * a.ldb * 2 >= (1ll << 31)) return false;
-  // (strip tiles only: shifted tap sets - valid convs and their dgrads - and wide images)
-  if (ch != 0 || cw != 0 || HW + HB_BM >= 65536 || a.aW + 2 > 255) return true;
-  // the halo slots of any 256-pixel tile must fit the stage
-  linear = halo_need(HB_BM, a.aH, a.aW, halo_pitch(a.aW)) <= HB_HPX &&
-           (a.N % HB_BN == 0 || n32_lin);
-  return true;
-}
-
-// MPA_HALO_WRES=0: no resident-weight variant (A/B of the 64-channel layers)
-static const bool g_halo_wres = [] {
-  const char* e = getenv("MPA_HALO_WRES");
-  return !(e && atoi(e) == 0);
-}();
-
-// ------------------------------------------------------------------ strip tiles (host)
-// MPA_HALO_STRIP: 0 off; 1 (default) images too wide for the linear tiles; 2 also the
-// resident-weight layers whose strips leave room for a third stage (ResNet layer1)
-static int g_strip = [] {
-  const char* e = getenv("MPA_HALO_STRIP");
-  return e ? atoi(e) : 1;
-}();
-void igemm_set_halo_strip(int mode) { g_strip = mode; }
-
-static bool strip_plan(const IGemmArgs& a, StripPlan& h, bool& wres, int& ns) {
-  const int W = a.oW, H = a.oH;  // tiles cover the output image
-  if ((a.N % HB_BN != 0 && a.N != 32) || W < 8) return false;
-  if (!tap_shift(a, h.ch, h.cw)) return false;
-  const int nstrip = (W + 127) / 128;
-  const int TW = (W + nstrip - 1) / nstrip;
-  int TR = std::max(1, std::min(H, HB_BM / TW));
-  const int P = (TW + 2 + 7) / 8 * 8;
-  while (TR > 1 && ((TR + 2) * P + 63) / 64 > HB_HIW) --TR;
-  const int hiw = ((TR + 2) * P + 63) / 64;
-  if (hiw > HB_HIW || 2 * TR * TW < HB_BM) return false;  // at least half the MFMA rows live
-  h.tr = TR;
-  h.tw = TW;
-  h.p = P;
-  h.hiw = hiw;
-  h.tiles_c = (W + TW - 1) / TW;
-  h.tiles_img = ((H + TR - 1) / TR) * h.tiles_c;
-  h.cc = a.aC / 32;
-  const int nimg = a.M / (H * W);  // (output pixels per image)
-  wres = g_halo_wres && (a.N + HB_BN - 1) / HB_BN == 1 && h.cc <= 2;
-  const int lds = 2 * HB_HBYTES + 2 * HB_WBYTES;
-  ns = 2;
-  if (wres && 3 * hiw * 4096 + h.cc * HB_WBYTES <= lds) ns = 3;
-  if (ns * hiw * 4096 + (wres ? h.cc : ns) * HB_WBYTES > lds) return false;
-  h.mag_tw = magic(TW);
-  h.mag_p = magic(P);
-  h.mag_tc = h.tiles_c > 1 ? magic(h.tiles_c) : 0u;
-  h.mag_timg = h.tiles_img > 1 ? magic(h.tiles_img) : 0u;
-  h.tiles_total = nimg * h.tiles_img * ((a.N + HB_BN - 1) / HB_BN);
-  return (int64_t)nimg * h.tiles_img < (1 << 24);
-}
-
-template <int EPI, int NJ = 4>
-static void launch_strip(bool wres, int ns, int grid, const IGemmArgs& a, const StripPlan& h,
-                         hipStream_t s) {
-  if (wres && ns == 3)
-    hipLaunchKernelGGL((conv3_strip_kernel<true, EPI, 3, NJ>), dim3(grid), dim3(512), 0, s, a, h);
-  else if (wres)
-    hipLaunchKernelGGL((conv3_strip_kernel<true, EPI, 2, NJ>), dim3(grid), dim3(512), 0, s, a, h);
-  else
-    hipLaunchKernelGGL((conv3_strip_kernel<false, EPI, 2, NJ>), dim3(grid), dim3(512), 0, s, a, h);
-}
-
-static int conv3_strip(IGemmArgs a, hipStream_t s) {
-  StripPlan h{};
-  bool wres;
-  int ns;
-  strip_plan(a, h, wres, ns);
-  for (int t = 0; t < 9; ++t) {
-    const int r = (a.Oh + a.taps.dh[t] - h.ch + 1) * 3 + (a.Ow + a.taps.dw[t] - h.cw + 1);
-    h.btoff[r] = a.taps.bt[t] * a.aC * 2;
-  }
-  h.a_bytes = (uint32_t)((int64_t)(a.M / ((int64_t)a.oH * a.oW)) * a.aH * a.aW * a.aC * 2);
-  h.b_bytes = (uint32_t)((int64_t)a.N * a.ldb * 2);
-  a.tiles_n = (a.N + HB_BN - 1) / HB_BN;
-  a.tiles_total = h.tiles_total;
-  int g8 = std::min(std::min(active_cus(), HALO_MAX_ROWS) / 8, (h.tiles_total + 7) / 8);
-  g8 = std::max(a.tiles_n, g8 / a.tiles_n * a.tiles_n);
-  const int grid = 8 * g8;
-  if (a.N == 32) {  // one 32-wide column tile (NJ = 2)
-    switch (halo_epi(a)) {
-      case 0: launch_strip<0, 2>(wres, ns, grid, a, h, s); break;
-      case EP_STATS: launch_strip<EP_STATS, 2>(wres, ns, grid, a, h, s); break;
-      case EP_BETA: launch_strip<EP_BETA, 2>(wres, ns, grid, a, h, s); break;
-      default: launch_strip<EP_BNRED, 2>(wres, ns, grid, a, h, s); break;
-    }
-    return grid;
-  }
-  switch (halo_epi(a)) {
-    case 0: launch_strip<0>(wres, ns, grid, a, h, s); break;
-    case EP_BETA: launch_strip<EP_BETA>(wres, ns, grid, a, h, s); break;
-    case EP_STATS: launch_strip<EP_STATS>(wres, ns, grid, a, h, s); break;
-    case EP_BIAS | EP_RELU: launch_strip<EP_BIAS | EP_RELU>(wres, ns, grid, a, h, s); break;
-    case EP_BIAS | EP_STATS: launch_strip<EP_BIAS | EP_STATS>(wres, ns, grid, a, h, s); break;
-    default: launch_strip<EP_BNRED>(wres, ns, grid, a, h, s); break;
-  }
-  return grid;
-}
-
-// strip tiles for this launch: images the linear tiles cannot hold, or (MPA_HALO_STRIP=2)
-// resident-weight layers that get a third stage
-static bool use_strip(const IGemmArgs& a, bool linear) {
-  if (g_strip < 1) return false;
-  StripPlan h{};
-  bool wres;
-  int ns;
-  if (!strip_plan(a, h, wres, ns)) return false;
-  return !linear || (g_strip >= 2 && ns == 3);
-}
-
-bool conv3_halo_ok(const IGemmArgs& a) {
-  bool linear;
-  if (!halo_ok_impl(a, linear)) return false;
-  return linear || use_strip(a, linear);
-}
-
-// Producer waves (PROD: 8-wave blocks, DMAs off the MFMA waves; each MFMA wave then has
-// 256 registers, which every flavour fits) for every launch: issuing the DMAs between the
-// MFMAs cost the MFMA waves ~10 % (round-2 A/B), and the fused BN-backward reduction
-// flavour, reduced per column group (TRED), fits 256 registers without scratch
-
-template <int EPI, int NJ>
-static void launch_halo_k(bool wres, int grid, const IGemmArgs& a, const HaloPlan& h,
-                          hipStream_t s, bool mi7 = false) {
-  if constexpr (NJ == 4 && (EPI == 0 || EPI == EP_STATS)) {
-    if (mi7) {  // (halo_mi7_ok: resident weights, whole 448-pixel tiles)
-      hipLaunchKernelGGL((conv3_halo_kernel<true, EPI, true, 4, 7>), dim3(grid), dim3(256), 0, s,
-                         a, h);
-      return;
-    }
-  }
-  const bool full = a.M % HB_BM == 0;  // no tile ends past M: branch-free epilogue everywhere
-  if (wres && full)
-    hipLaunchKernelGGL((conv3_halo_kernel<true, EPI, true, NJ>), dim3(grid), dim3(512), 0, s, a, h);
-  else if (wres)
-    hipLaunchKernelGGL((conv3_halo_kernel<true, EPI, false, NJ>), dim3(grid), dim3(512), 0, s, a, h);
-  else if (full)
-    hipLaunchKernelGGL((conv3_halo_kernel<false, EPI, true, NJ>), dim3(grid), dim3(512), 0, s, a, h);
-  else
-    hipLaunchKernelGGL((conv3_halo_kernel<false, EPI, false, NJ>), dim3(grid), dim3(512), 0, s, a, h);
-}
-
-template <int EPI>
-static void launch_halo(bool wres, int grid, const IGemmArgs& a, const HaloPlan& h,
-                        hipStream_t s, bool mi7 = false) {
-  launch_halo_k<EPI, 4>(wres, grid, a, h, s, mi7);
-}
-
-// MPA_HALO_MI7=0: keep the 256-pixel tiles for the resident-weight layers (A/B)
-static int g_halo_mi7 = [] {
-  const char* e = getenv("MPA_HALO_MI7");
-  return e ? atoi(e) : 1;
-}();
-void igemm_set_halo_mi7(int on) { g_halo_mi7 = on; }
-
-// 448-pixel tiles (MI = 7): same-conv tap set, one resident 64-wide weight tile, tiles of
-// whole image rows that never cross an image (HW % 448 == 0, 448 % W == 0) and whose
-// (448 / W + 2)-slot halo fits the 640-pixel stage
-static bool halo_mi7_ok(const IGemmArgs& a, int epi, bool wres) {
-  if (!g_halo_mi7 || !wres || a.N != HB_BN) return false;
-  // (the accumulate / BN-link dgrad flavours spill 92-102 B/lane at 448 pixels: not yet)
-  if (epi != 0 && epi != EP_STATS) return false;
-  int ch, cw;
-  if (!tap_shift(a, ch, cw) || ch != 0 || cw != 0) return false;
-  const int64_t HW = (int64_t)a.aH * a.aW;
-  constexpr int BM7 = 448;
-  if (HW % BM7 != 0 || BM7 % a.aW != 0 || a.M % BM7 != 0) return false;
-  return (BM7 / a.aW + 2) * halo_pitch(a.aW) <= 640;
-}
-
-// N == 32 (plain and statistics epilogues only; producer-wave blocks)
-template <int EPI>
-static void launch_halo32(bool wres, int grid, const IGemmArgs& a, const HaloPlan& h,
-                          hipStream_t s) {
-  launch_halo_k<EPI, 2>(wres, grid, a, h, s);
-}
-
-// Launch (conv3_halo_ok(a) must hold; B K-contiguous with the tap map in a.taps.bt);
-// returns the number of statistics-slab rows written (one per block, <= HALO_MAX_ROWS).
-int conv3_halo(IGemmArgs a, hipStream_t s) {
-  {
-    bool linear;
-    halo_ok_impl(a, linear);
-    if (use_strip(a, linear)) return conv3_strip(a, s);
-  }
-  HaloPlan h{};
-  const int W2 = halo_pitch(a.aW);
-  h.w2 = W2;
-  for (int t = 0; t < 9; ++t) {  // raster (dh, dw) order, whatever order the table had
-    const int r = (a.Oh + a.taps.dh[t] + 1) * 3 + (a.Ow + a.taps.dw[t] + 1);
-    h.btoff[r] = a.taps.bt[t] * a.aC * 2;
-  }
-  h.mag_w = magic(a.aW);
-  h.mag_w2 = magic(W2);
-  h.mag_h1 = magic(a.aH + 1);
-  h.mag_hw = magic(a.aH * a.aW);
-  h.cc = a.aC / 32;
-  h.hiw = conv3_halo_dma_count(a.aH, a.aW);
-  const bool wres = g_halo_wres && (a.N + HB_BN - 1) / HB_BN == 1 && h.cc <= 2;
-  const bool mi7 = halo_mi7_ok(a, halo_epi(a), wres);
-  h.tiles_m = mi7 ? a.M / 448 : (a.M + HB_BM - 1) / HB_BM;
-  a.tiles_n = (a.N + HB_BN - 1) / HB_BN;
-  h.tiles_total = h.tiles_m * a.tiles_n;
-  a.tiles_total = h.tiles_total;
-  h.a_bytes = (uint32_t)((int64_t)a.M * a.aC * 2);
-  h.b_bytes = (uint32_t)((int64_t)a.N * a.ldb * 2);
-  // persistent grid: G8 blocks per XCD, a multiple of tiles_n (fixed column tile per block)
-  int g8 = std::min(std::min(active_cus(), HALO_MAX_ROWS) / 8, (h.tiles_total + 7) / 8);
-  g8 = std::max(a.tiles_n, g8 / a.tiles_n * a.tiles_n);
-  const int grid = 8 * g8;
-  if (a.N == 32) {
-    if (halo_epi(a) == EP_STATS) launch_halo32<EP_STATS>(wres, grid, a, h, s);
-    else launch_halo32<0>(wres, grid, a, h, s);
-    return grid;
-  }
-  switch (halo_epi(a)) {
-    case 0: launch_halo<0>(wres, grid, a, h, s, mi7); break;
-    case EP_BETA: launch_halo<EP_BETA>(wres, grid, a, h, s); break;
-    case EP_STATS: launch_halo<EP_STATS>(wres, grid, a, h, s, mi7); break;
-    case EP_BIAS | EP_RELU: launch_halo<EP_BIAS | EP_RELU>(wres, grid, a, h, s); break;
-    case EP_BIAS | EP_STATS: launch_halo<EP_BIAS | EP_STATS>(wres, grid, a, h, s); break;
-    default: launch_halo<EP_BNRED>(wres, grid, a, h, s); break;
-  }
-  return grid;
-}
-
-// ------------------------------------------------------------------ halo wgrad host
-static int halo_wgrad_pitch(int W) { return (W + 2 + 15) / 16 * 16; }
-
-// shape checks shared by the linear and strip tilings
-// (pad 1: same conv; pad 0: valid conv, strip tiles only - its dy is the smaller image)
-static bool halo_wgrad_base(const WGradArgs& a) {
-  if (!g_halo || a.R != 3 || a.S != 3 || a.sh != 1 || a.sw != 1) return false;
-  if (a.ph < 0 || a.ph > 1 || a.pw < 0 || a.pw > 1) return false;
-  if (a.P != a.H + 2 * a.ph - 2 || a.Q != a.W + 2 * a.pw - 2 || a.P <= 0 || a.Q <= 0) return false;
-  // 64 x 64 partitions; a 32-wide remainder in either dimension is zero-filled
-  if (a.C % 32 != 0 || a.Kout % 32 != 0) return false;
-  const int64_t PQ = (int64_t)a.P * a.Q;
-  if (a.Mpix % PQ != 0) return false;
-  const int64_t nimg = a.Mpix / PQ;
-  return nimg * a.H * a.W * a.C * 2 < (1ll << 31) && (int64_t)a.Mpix * a.Kout * 2 < (1ll << 31);
-}
-
-// strip tiling of the weight gradient (images too wide for the linear tiles): the TR x TW
-// tile (TR * TW <= 128 pixels) minimising tiles x (128 MFMA rows + staged halo pixels)
-static bool halo_wgrad_strip_plan(const WGradArgs& a, HaloWPlan& h) {
-  if (g_strip < 1 || !halo_wgrad_base(a)) return false;
-  const int OH = a.P, OW = a.Q;  // tiles cover dy (the conv output)
-  const int64_t nimg = a.Mpix / ((int64_t)OH * OW);
-  int64_t best = -1;
-  for (int n = 1; n <= OW; ++n) {
-    const int tw = (OW + n - 1) / n;
-    if (tw > 126 || (n > 1 && (OW + tw - 1) / tw != n)) continue;
-    if (tw < 8) break;
-    const int pitch = (tw + 2 + 15) / 16 * 16;
-    int tr = std::max(1, std::min(OH, HW_BM / tw));
-    while (tr > 1 && (tr + 2) * pitch > HW_HPX) --tr;
-    if ((tr + 2) * pitch > HW_HPX) continue;
-    const int64_t tiles = nimg * ((OH + tr - 1) / tr) * n;
-    const int64_t cost = tiles * (HW_BM + (tr + 2) * pitch);
-    if (best < 0 || cost < best) {
-      best = cost;
-      h.tr = tr;
-      h.tw = tw;
-      h.w2 = pitch;
-      h.tiles_c = n;
-      h.tiles_img = ((OH + tr - 1) / tr) * n;
-      h.tiles_m = (int)tiles;
-    }
-  }
-  if (best < 0 || h.tiles_m <= 0) return false;
-  h.mag_tw = magic(h.tw);
-  h.mag_tc = h.tiles_c > 1 ? magic(h.tiles_c) : 0u;
-  h.mag_timg = h.tiles_img > 1 ? magic(h.tiles_img) : 0u;
-  return true;
-}
-
-static bool halo_wgrad_geom(const WGradArgs& a) {
-  if (!halo_wgrad_base(a) || a.ph != 1 || a.pw != 1) return false;
-  const int64_t HW = (int64_t)a.H * a.W;
-  if (HW + HW_BM >= 65536 || a.W + 2 > 255) return false;
-  // 32-channel partitions may use both chunk areas for one wider halo image (ONECH)
-  return halo_need(HW_BM, a.H, a.W, halo_wgrad_pitch(a.W)) <= (a.C == 32 ? 2 : 1) * HW_HPX;
-}
-
-// one 32-channel chunk whose halo needs the combined image
-static bool halo_wgrad_onech(const WGradArgs& a) {
-  return a.C == 32 && halo_need(HW_BM, a.H, a.W, halo_wgrad_pitch(a.W)) > HW_HPX;
-}
-
-// Halo DMA instructions per wave and chunk of the 4-wave linear-tile weight gradient on
-// H x W images: the smallest instantiated count (HT, see launch_halo_wgrad) that covers
-// the slots a tile reads.  Instantiated next to the pitch: 4 of 7 at pitch 16 (ResNet
-// layer3), 5 of 7 at pitch 32 (layer2).
-int conv3_halo_wgrad_dma_count(int H, int W) {
-  const int W2 = halo_wgrad_pitch(W);
-  const int64_t need = halo_need(HW_BM, H, W, W2);
-  if (need > HW_HPX) return HW_HIW;  // (ONECH / strip tiles: whole stages)
-  const int c = halo_dma_count(need, HW_HIW);
-  if (W2 == 16 && c <= 4) return 4;
-  if (W2 == 32 && c <= 5) return 5;
-  return HW_HIW;
-}
+int conv3_halo_wgrad_dma_count(int H, int W) { return halo_wgrad_dma_count(H, W, g_sw.trim); }
 
 int64_t conv3_halo_wgrad_ws_floats(int Kout, int Ncols) {
   if (Ncols % 9 != 0 || (Ncols / 9) % 32 != 0 || Kout % 32 != 0) return 0;
   return (int64_t)HALO_MAX_ROWS * 64 * 64 * 9;  // <= 256 blocks x one 64x9x64 partition
 }
 
+HaloLaunch conv3_halo_plan(const IGemmArgs& a) { return plan_halo(a, g_sw, active_cus()); }
+bool conv3_halo_ok(const IGemmArgs& a) { return conv3_halo_plan(a).kind != HaloKind::None; }
+
+HaloWLaunch conv3_halo_wgrad_plan(const WGradArgs& a) {
+  if (a.slab == nullptr) return HaloWLaunch{};
+  return plan_halo_wgrad(a, g_sw, active_cus());
+}
 bool conv3_halo_wgrad_ok(const WGradArgs& a) {
-  if (a.slab == nullptr) return false;
-  if (halo_wgrad_geom(a)) return true;
-  HaloWPlan h{};
-  return halo_wgrad_strip_plan(a, h);
+  return conv3_halo_wgrad_plan(a).kind != HaloWKind::None;
+}
+
+// Producer waves (8-wave blocks, DMAs off the MFMA waves; each MFMA wave then has 256
+// registers, which every flavour fits) for every 256-pixel and strip launch: issuing the
+// DMAs between the MFMAs cost the MFMA waves ~10 % (round-2 A/B), and the fused BN-backward
+// reduction flavour, reduced per column group (TRED), fits 256 registers without scratch.
+// m: MI of a linear tile (4, or 7 for 448 pixels), NS of a strip tile
+static constexpr int halo_key(bool strip, bool wres, int epi, bool full, int nj, int m) {
+  return ((((strip * 2 + wres) * 32 + epi) * 2 + full) * 8 + nj) * 8 + m;
+}
+
+// Launch the instance L names (L = conv3_halo_plan(a), not None; B K-contiguous with the
+// tap map in a.taps.bt); returns the number of statistics-slab rows written (one per
+// block, <= HALO_MAX_ROWS).
+int conv3_halo(IGemmArgs a, const HaloLaunch& L, hipStream_t s) {
+  a.tiles_n = L.tiles_n;
+  a.tiles_total = L.tiles_total;
+  const dim3 grid(L.grid), block(L.threads);
+  const bool strip = L.kind == HaloKind::Strip;
+  const int m = strip ? L.ns : L.kind == HaloKind::Linear448 ? 7 : 4;
+#define LIN(WRES, EPI, FULL, NJ, MI)                                                       \
+  case halo_key(false, WRES, EPI, FULL, NJ, MI):                                           \
+    hipLaunchKernelGGL((conv3_halo_kernel<WRES, EPI, FULL, NJ, MI>), grid, block, 0, s, a, \
+                       L.lin);                                                             \
+    break;
+#define LIN4(EPI, NJ) \
+  LIN(true, EPI, true, NJ, 4) LIN(true, EPI, false, NJ, 4) LIN(false, EPI, true, NJ, 4) \
+  LIN(false, EPI, false, NJ, 4)
+#define STRIP(WRES, EPI, NS, NJ)                                                        \
+  case halo_key(true, WRES, EPI, false, NJ, NS):                                        \
+    hipLaunchKernelGGL((conv3_strip_kernel<WRES, EPI, NS, NJ>), grid, block, 0, s, a,   \
+                       L.strip);                                                        \
+    break;
+#define STRIP3(EPI, NJ) STRIP(true, EPI, 3, NJ) STRIP(true, EPI, 2, NJ) STRIP(false, EPI, 2, NJ)
+  switch (halo_key(strip, L.wres, L.epi, L.full, L.nj, m)) {
+    STRIP3(0, 2) STRIP3(EP_STATS, 2) STRIP3(EP_BETA, 2) STRIP3(EP_BNRED, 2)
+    STRIP3(0, 4) STRIP3(EP_BETA, 4) STRIP3(EP_STATS, 4) STRIP3(EP_BIAS | EP_RELU, 4)
+    STRIP3(EP_BIAS | EP_STATS, 4) STRIP3(EP_BNRED, 4)
+    LIN4(EP_STATS, 2) LIN4(0, 2)
+    LIN(true, 0, true, 4, 7) LIN4(0, 4) LIN4(EP_BETA, 4)
+    LIN(true, EP_STATS, true, 4, 7) LIN4(EP_STATS, 4) LIN4(EP_BIAS | EP_RELU, 4)
+    LIN4(EP_BIAS | EP_STATS, 4) LIN4(EP_BNRED, 4)
+    default:
+      fprintf(stderr, "conv3_halo: the plan names no instantiated kernel\n");
+      abort();
+  }
+#undef LIN
+#undef LIN4
+#undef STRIP
+#undef STRIP3
+  return L.grid;
 }
 
 // Producer-wave weight-gradient kernels (PROD) for the linear tiles: the 13 ResNet-18 halo
 // weight gradients take 3.14 ms instead of 3.63 ms per b1024 step, +2.4 % single-stream
 // (round-5 A/B, profiles/wprod_pre_ab_r5.txt).  MPA_HALO_WPROD=0: the 4-wave form (the
 // MFMA waves issue the DMAs).
-// XCD-grouped weight-gradient block order (HaloWPlan::xmap); MPA_HALO_WXMAP=0: plain order
-static bool g_wxmap = [] {
-  const char* e = getenv("MPA_HALO_WXMAP");
-  return !(e && e[0] == '0');
-}();
-
-static bool g_wprod = [] {
-  const char* e = getenv("MPA_HALO_WPROD");
-  return !(e && e[0] == '0');
-}();
-void igemm_set_halo_wprod(int on) { g_wprod = on != 0; }
-void igemm_set_halo_wxmap(int on) { g_wxmap = on != 0; }
-
-// (8-wave forms use the run-time pitch: with a compile-time pitch the MFMA waves' hoisted
-// tap addresses spill past their 256 registers)
-template <int W2T, bool ONECH = false, bool STRIP = false>
-static void launch_halo_wgrad(const WGradArgs& a, const HaloWPlan& h, dim3 grid, hipStream_t s) {
-  if constexpr (!STRIP) {
-    if (g_wprod) {
-      if (a.Kout == 32)
-        hipLaunchKernelGGL((conv3_halo_wgrad_kernel<0, ONECH, false, true, 2>), grid,
-                           dim3(512), 0, s, a, h);
-      else
-        hipLaunchKernelGGL((conv3_halo_wgrad_kernel<0, ONECH, false, true>), grid,
-                           dim3(512), 0, s, a, h);
-      return;
-    }
-  }
-  // 4-wave form: the geometry-sized halo fetch where a count is instantiated for the pitch
-  if constexpr (!ONECH && !STRIP && (W2T == 16 || W2T == 32)) {
-    constexpr int HT = W2T == 16 ? 4 : 5;
-    if (conv3_halo_wgrad_dma_count(a.H, a.W) == HT) {
-      hipLaunchKernelGGL((conv3_halo_wgrad_kernel<W2T, false, false, false, 4, HT>), grid,
-                         dim3(256), 0, s, a, h);
-      return;
-    }
-  }
-  hipLaunchKernelGGL((conv3_halo_wgrad_kernel<W2T, ONECH, STRIP>), grid, dim3(256), 0, s, a, h);
+static constexpr int halo_wkey(int w2t, HaloWKind kind, bool prod, int km, int ht) {
+  return (((w2t * 4 + (int)kind) * 2 + prod) * 8 + km) * 8 + ht;
 }
 
-// slab partials -> returns Z (slabs of [Kout][9C] to sum into dw)
-int conv3_halo_wgrad(WGradArgs a, hipStream_t s) {
-  HaloWPlan h{};
-  if (!halo_wgrad_geom(a) && halo_wgrad_strip_plan(a, h)) {
-    const int W2 = h.w2;
-    for (int t = 0; t < 9; ++t) h.toff[t] = (t / 3 - 1) * W2 + (t % 3 - 1);
-    h.mag_w2 = magic(W2);
-    h.kparts = (a.Kout + 63) / 64;
-    h.parts = h.kparts * ((a.C + 63) / 64);
-    const int G = std::min(active_cus(), HALO_MAX_ROWS);
-    h.Z = std::max(1, std::min(G / h.parts, h.tiles_m));
-    h.dy_bytes = (uint32_t)((int64_t)a.Mpix * a.Kout * 2);
-    h.x_bytes = (uint32_t)((int64_t)(a.Mpix / ((int64_t)a.P * a.Q)) * a.H * a.W * a.C * 2);
-    h.xmap = g_wxmap && (h.parts * h.Z) % 8 == 0;
-    launch_halo_wgrad<0, false, true>(a, h, dim3(h.parts * h.Z), s);
-    return h.Z;
+// Launch the instance L names (L = conv3_halo_wgrad_plan(a), not None): slab partials;
+// returns Z (slabs of [Kout][9C] to sum into dw)
+int conv3_halo_wgrad(const WGradArgs& a, const HaloWLaunch& L, hipStream_t s) {
+  const dim3 grid(L.grid), block(L.threads);
+#define WG(W2T, KIND, PROD, KM, HT)                                                        \
+  case halo_wkey(W2T, HaloWKind::KIND, PROD, KM, HT):                                      \
+    hipLaunchKernelGGL((conv3_halo_wgrad_kernel<W2T, HaloWKind::KIND == HaloWKind::OneChunk, \
+                                                HaloWKind::KIND == HaloWKind::Strip, PROD, \
+                                                KM, HT>),                                  \
+                       grid, block, 0, s, a, L.plan);                                      \
+    break;
+  switch (halo_wkey(L.w2t, L.kind, L.prod, L.km, L.ht)) {
+    WG(0, Strip, false, 4, 7)
+    WG(0, OneChunk, true, 2, 7) WG(0, OneChunk, true, 4, 7) WG(0, OneChunk, false, 4, 7)
+    WG(0, Linear, true, 2, 7) WG(0, Linear, true, 4, 7)
+    WG(16, Linear, false, 4, 4) WG(16, Linear, false, 4, 7)
+    WG(32, Linear, false, 4, 5) WG(32, Linear, false, 4, 7)
+    WG(48, Linear, false, 4, 7) WG(64, Linear, false, 4, 7) WG(0, Linear, false, 4, 7)
+    default:
+      fprintf(stderr, "conv3_halo_wgrad: the plan names no instantiated kernel\n");
+      abort();
   }
-  const int W2 = halo_wgrad_pitch(a.W);
-  h.w2 = W2;
-  for (int t = 0; t < 9; ++t) h.toff[t] = (t / 3 - 1) * W2 + (t % 3 - 1);
-  h.mag_w = magic(a.W);
-  h.mag_w2 = magic(W2);
-  h.mag_h1 = magic(a.H + 1);
-  h.mag_hw = magic(a.H * a.W);
-  h.tiles_m = (a.Mpix + HW_BM - 1) / HW_BM;
-  h.kparts = (a.Kout + 63) / 64;
-  h.parts = h.kparts * ((a.C + 63) / 64);
-  const int G = std::min(active_cus(), HALO_MAX_ROWS);
-  h.Z = std::max(1, std::min(G / h.parts, h.tiles_m));
-  h.dy_bytes = (uint32_t)((int64_t)a.Mpix * a.Kout * 2);
-  h.x_bytes = (uint32_t)((int64_t)a.Mpix * a.C * 2);
-  const dim3 grid(h.parts * h.Z);
-  h.xmap = g_wxmap && (h.parts * h.Z) % 8 == 0;
-  if (halo_wgrad_onech(a)) {
-    launch_halo_wgrad<0, true>(a, h, grid, s);
-    return h.Z;
-  }
-  switch (W2) {
-    case 16: launch_halo_wgrad<16>(a, h, grid, s); break;
-    case 32: launch_halo_wgrad<32>(a, h, grid, s); break;
-    case 48: launch_halo_wgrad<48>(a, h, grid, s); break;
-    case 64: launch_halo_wgrad<64>(a, h, grid, s); break;
-    default: launch_halo_wgrad<0>(a, h, grid, s); break;
-  }
-  return h.Z;
+#undef WG
+  return L.plan.Z;
 }
 
 }  // namespace mpa

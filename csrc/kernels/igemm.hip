@@ -33,6 +33,7 @@
 #include <mutex>
 #include <string>
 #include "igemm_common.h"
+#include "halo_plan.h"
 
 namespace mpa {
 
@@ -875,12 +876,13 @@ static void run_rows(IGemmArgs a, bool bkc, int vw, float* ws, float* slab, hipS
     if (stats) slab_stats(slab, rows, a.N, a.stats_shift, a.M, sums, stats, s, a.stats_ld);
     return;
   }
-  if (dma && bkc && conv3_halo_ok(a)) {  // 3x3 / stride 1: halo-staged direct conv
+  const HaloLaunch halo = dma && bkc ? conv3_halo_plan(a) : HaloLaunch{};
+  if (halo.kind != HaloKind::None) {  // 3x3 / stride 1: halo-staged direct conv
     float* stats = a.stats;
     float* sums = stats ? slab + slab_rows_max(a.M) * 2 * a.N : nullptr;
     a.stats = stats ? slab : nullptr;
     a.stats_sums = sums;
-    const int rows = conv3_halo(a, s);
+    const int rows = conv3_halo(a, halo, s);
     if (stats) slab_stats(slab, rows, a.N, a.stats_shift, a.M, sums, stats, s, a.stats_ld);
     return;
   }
@@ -1006,8 +1008,9 @@ void igemm_rows_dgrad_bnred(IGemmArgs a, int vw, bool bkc, float* slab, float* s
   if (a.nphase == 0 && bkc) {
     IGemmArgs t = a;
     if (t.ep_gamma && t.ep_beta) t.ep_y = nullptr;  // the halo kernel's z-mask form
-    if (conv3_halo_ok(t)) {
-      rows = conv3_halo(t, s);
+    const HaloLaunch halo = conv3_halo_plan(t);
+    if (halo.kind != HaloKind::None) {
+      rows = conv3_halo(t, halo, s);
       slab_reduce(slab, rows, 2 * a.N, sums, false, s);
       return;
     }
@@ -1224,8 +1227,9 @@ static void tuned_wgrad_tile(const WGradArgs& a, int vwa, int vwb, hipStream_t s
 }
 
 void igemm_wgrad(WGradArgs a, int vwa, int vwb, hipStream_t s) {
-  if (igemm_engine() >= 1 && conv3_halo_wgrad_ok(a)) {  // 3x3 / stride 1: halo-staged
-    const int z = conv3_halo_wgrad(a, s);
+  const HaloWLaunch halo = igemm_engine() >= 1 ? conv3_halo_wgrad_plan(a) : HaloWLaunch{};
+  if (halo.kind != HaloWKind::None) {  // 3x3 / stride 1: halo-staged
+    const int z = conv3_halo_wgrad(a, halo, s);
     const int64_t n = (int64_t)a.Kout * a.Ncols;  // Ncols = 9C, C % 32 == 0: float4 rows
     const int blocks = (int)std::max<int64_t>(1, (n / 4 + 63) / 64);
     hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(blocks), dim3(256), 0, s, a.slab, z, n, a.dw,

@@ -4,7 +4,11 @@ magic-number divisions, slot blocks dealt round-robin over the four DMA waves an
 by the geometry-sized per-wave DMA count) and check that every fragment read of every tap
 lands on the right input pixel (or on a zero), in a slot that was fetched and that lies
 below `need`, the slot count the host sizes the fetch by.  Run before launching a changed
-kernel:  python tools/halo_index_check.py"""
+kernel:  python tools/halo_index_check.py
+
+The definition of halo_need, the DMA count and the two pitches is csrc/kernels/halo_plan.h
+(what the host launches); the functions of those names here are an emulation of it, checked
+against the header for every H, W in 1..64 by tests/test_halo_plan_cpu.py."""
 import itertools
 
 NW = 4  # DMA waves per block; one DMA instruction fetches a block of 16 slots
@@ -19,7 +23,7 @@ def udiv(n, m):
 
 
 def halo_need(BM, H, W, W2):
-    """conv_halo.hip halo_need(): slots any BM-pixel linear tile can read - the rows it
+    """halo_plan.h halo_need(): slots any BM-pixel linear tile can read - the rows it
     touches, 2 halo rows and the image separators it crosses, times the pitch (+1: with
     pitch W + 1 the last slot's right border is the next pixel)."""
     rows = (BM - 1 + W - 1) // W + 1
@@ -28,7 +32,7 @@ def halo_need(BM, H, W, W2):
 
 
 def dma_count(need, hiw_max):
-    """conv_halo.hip halo_dma_count(): 16-slot DMA instructions per wave covering `need`"""
+    """halo_plan.h halo_dma_count(): 16-slot DMA instructions per wave covering `need`"""
     blocks = (need + 15) // 16
     return min(hiw_max, (blocks + NW - 1) // NW)
 
