@@ -1,9 +1,10 @@
 // Torch-facing binding layer for the gfx950 kernel library (module mpi_pytorch_amd._C).
 //
 // Responsibilities: validate dtypes/shapes/contiguity (so a kernel never sees operands its
-// grid does not expect), allocate outputs on the caller's device, build the implicit-GEMM
-// tap tables, and launch on the current HIP stream (so everything composes with HIP
-// graphs and the RCCL comm stream).  The function set mirrors ops/ref.py one-to-one.
+// grid does not expect), allocate outputs on the caller's device, fill in the operands of
+// the launch geometry that kernels/conv_args.h derives from the shapes, and launch on the
+// current HIP stream (so everything composes with HIP graphs and the RCCL comm stream).
+// The function set mirrors ops/ref.py one-to-one.
 #include <torch/extension.h>
 #include <c10/hip/HIPStream.h>
 #include <c10/core/DeviceGuard.h>
@@ -11,6 +12,7 @@
 #include <vector>
 
 #include "kernels/api.h"
+#include "kernels/conv_args.h"
 #include "runtime/runtime.h"
 
 using torch::Tensor;
@@ -94,8 +96,12 @@ static Tensor conv_fwd_impl(Tensor x, Tensor w, Tensor bias, int64_t sh, int64_t
   const int N = x.size(0), H = x.size(1), W = x.size(2), C = x.size(3);
   const int K = w.size(0), R = w.size(1), S = w.size(2);
   TORCH_CHECK(w.size(3) == C, "conv_fwd: channel mismatch");
-  TORCH_CHECK(R * S <= mpa::MAXT, "conv_fwd: too many taps");
-  const int P = (H + 2 * ph - R) / sh + 1, Q = (W + 2 * pw - S) / sw + 1;
+  mpa::IGemmArgs a;
+  const char* limit =
+      mpa::conv_fwd_args({N, H, W, C, K, R, S, (int)sh, (int)sw, (int)ph, (int)pw},
+                         C == 8 && S > 1 && mpa::igemm_stap_ok(), a);
+  TORCH_CHECK(!limit, "conv_fwd: ", limit);
+  const int P = a.oH, Q = a.oW;
   TORCH_CHECK(P > 0 && Q > 0, "conv_fwd: empty output");
   if (has(bias)) TORCH_CHECK(bias.numel() == K, "conv_fwd: bias size");
   int stats_ld = 0;
@@ -126,34 +132,9 @@ static Tensor conv_fwd_impl(Tensor x, Tensor w, Tensor bias, int64_t sh, int64_t
   } else {
     y = empty_like_shape(x, {N, P, Q, K}, torch::kBFloat16);
   }
-  mpa::IGemmArgs a{};
-  a.A = bp(x); a.aH = H; a.aW = W; a.aC = C;
-  a.oH = P; a.oW = Q; a.M = N * P * Q;
-  a.Uh = sh; a.Uw = sw; a.Oh = -ph; a.Ow = -pw;
-  a.T = R * S;
-  for (int r = 0; r < R; ++r)
-    for (int s = 0; s < S; ++s) {
-      const int t = r * S + s;
-      a.taps.dh[t] = r; a.taps.dw[t] = s; a.taps.bt[t] = t;
-    }
-  a.Ktot = a.T * C;
-  a.B = bp(w); a.N = K; a.RS = R * S; a.ldb = a.Ktot;
-  if (C == 8 && S > 1 && mpa::igemm_stap_ok()) {
-    // 8-channel image stem: group 4 adjacent kernel columns into one 32-deep K tile (their
-    // input pixels are 64 contiguous bytes in NHWC), so the stem takes the uniform-tap
-    // fast path; columns past S get zero weights.  K grows from R*S*8 to R*ceil(S/4)*32.
-    int t = 0;
-    for (int r = 0; r < R; ++r)
-      for (int s0 = 0; s0 < S; s0 += 4, ++t) {
-        a.taps.dh[t] = r; a.taps.dw[t] = s0;
-        a.taps.bt[t] = (short)((r * S + s0) | (std::min(4, S - s0) << 12));
-      }
-    a.T = t;
-    a.Ktot = t * 32;
-    a.stap = 1;
-  }
+  a.A = bp(x);
+  a.B = bp(w);
   a.C = y.data_ptr(); a.ldc = ldc;
-  a.dH = P; a.dW = Q; a.Uoh = 1; a.Uow = 1; a.Poh = 0; a.Pow = 0;
   a.bias = fopt(bias);
   if (stats_ld) {  // a checked [2, K] row-window of a wider table
     CHECK_CUDA(stats);
@@ -211,6 +192,7 @@ static Tensor conv_dgrad_impl(Tensor dy, Tensor w, int64_t H, int64_t W, int64_t
   const int N = dy.size(0), P = dy.size(1), Q = dy.size(2), K = dy.size(3);
   const int Kw = w.size(0), R = w.size(1), S = w.size(2), C = w.size(3);
   TORCH_CHECK(Kw == K, "conv_dgrad: channel mismatch");
+  // (conv_dgrad_args tests this too; here it still comes before the accum checks)
   TORCH_CHECK(R * S <= mpa::MAXT, "conv_dgrad: too many taps");
   const c10::OptionalDeviceGuard g(device_of(dy));
   // accum: dx accumulates into this tensor (a second gradient contribution to the same
@@ -228,56 +210,23 @@ static Tensor conv_dgrad_impl(Tensor dy, Tensor w, int64_t H, int64_t W, int64_t
     dx = empty_like_shape(dy, {N, (int64_t)H, (int64_t)W, C}, torch::kBFloat16);
   }
   const int vw = std::min(vec_width(K), vec_width(C));
-  // sub-pixel decomposition: output phase (a_, b_) of dx is a stride-1 conv of dy with the
-  // taps (r, s) congruent to it; stride 1 has one phase
-  mpa::IGemmArgs a{};
-  a.A = bp(dy); a.aH = P; a.aW = Q; a.aC = K;
-  a.Uh = 1; a.Uw = 1; a.Oh = 0; a.Ow = 0;
-  a.B = bp(w); a.N = C; a.RS = R * S; a.ldb = C;
   const bool bkc = wt_opt && wt_opt->defined() && wt_opt->numel() == w.numel() && vw == 8;
   if (bkc) {
     CHECK_ACT((*wt_opt));
-    a.B = bp(*wt_opt);
-    a.ldb = R * S * K;
-    a.b_tapmap = 1;
   }
+  // the stride phases and their taps; `empty`: some phase has none (stride > kernel)
+  mpa::DgradSrc2Shape s2{};
+  if (src2) s2 = {(int)src2->w2.size(1), (int)src2->w2.size(2), src2->ph2, src2->pw2};
+  mpa::IGemmArgs a;
+  bool empty;
+  const char* limit =
+      mpa::conv_dgrad_args({N, (int)H, (int)W, C, K, R, S, (int)sh, (int)sw, (int)ph, (int)pw}, P,
+                           Q, bkc, src2 ? &s2 : nullptr, a, empty);
+  TORCH_CHECK(!limit, "conv_dgrad: ", limit);
+  a.A = bp(dy);
+  a.B = bkc ? bp(*wt_opt) : bp(w);
   a.C = dx.data_ptr(); a.ldc = C;
-  a.dH = H; a.dW = W; a.Uoh = sh; a.Uow = sw;
-  a.bias = nullptr; a.stats = nullptr; a.relu = 0;
   a.beta = acc ? 1 : 0;
-  int T = 0, nph = 0;
-  for (int a_ = 0; a_ < sh; ++a_)
-    for (int b_ = 0; b_ < sw; ++b_) {
-      const int Hp = (H - a_ + sh - 1) / sh, Wp = (W - b_ + sw - 1) / sw;
-      if (Hp <= 0 || Wp <= 0) continue;
-      const int t0 = T;
-      for (int r = 0; r < R; ++r) {
-        if (((a_ + ph - r) % sh) != 0) continue;
-        for (int s = 0; s < S; ++s) {
-          if (((b_ + pw - s) % sw) != 0) continue;
-          a.taps.dh[T] = (a_ + ph - r) / sh;
-          a.taps.dw[T] = (b_ + pw - s) / sw;
-          a.taps.bt[T] = r * S + s;
-          ++T;
-        }
-      }
-      if (src2) {
-        const int R2 = src2->w2.size(1), S2 = src2->w2.size(2);
-        for (int r = 0; r < R2; ++r) {
-          if (((a_ + src2->ph2 - r) % sh) != 0) continue;
-          for (int s = 0; s < S2; ++s) {
-            if (((b_ + src2->pw2 - s) % sw) != 0) continue;
-            TORCH_CHECK(T < mpa::MAXT, "conv_dgrad: too many taps");
-            a.taps.dh[T] = (a_ + src2->ph2 - r) / sh;
-            a.taps.dw[T] = (b_ + src2->pw2 - s) / sw;
-            a.taps.bt[T] = (short)((r * S2 + s) | mpa::TAP_SRC2);
-            ++T;
-          }
-        }
-      }
-      TORCH_CHECK(nph < mpa::MAXPH, "conv_dgrad: too many stride phases");
-      a.ph[nph++] = mpa::PhaseDesc{N * Hp * Wp, Hp, Wp, (T - t0) * K, t0, T - t0, a_, b_, 0};
-    }
   if (bnred) {
     a.ep_z = bp(bnred->z);
     a.ep_y = bopt(bnred->y);
@@ -293,20 +242,7 @@ static Tensor conv_dgrad_impl(Tensor dy, Tensor w, int64_t H, int64_t W, int64_t
     for (const Tensor* t : {&bnred->mean, &bnred->rstd, &bnred->gamma, &bnred->beta})
       TORCH_CHECK(!has(*t) || t->numel() == C, "conv_dgrad_bnred: per-channel vector size");
     bnred->sums = torch::empty({2 * C}, dy.options().dtype(torch::kFloat32));
-    int k = 0;
-    bool empty = false;
-    for (int i = 0; i < nph; ++i) {
-      empty |= a.ph[i].T == 0;
-      if (a.ph[i].T > 0) a.ph[k++] = a.ph[i];
-    }
     if (empty) dx.zero_();
-    if (sh == 1 && sw == 1) {
-      const mpa::PhaseDesc& d = a.ph[0];
-      a.M = d.M; a.oH = d.oH; a.oW = d.oW; a.T = d.T; a.Ktot = d.Ktot; a.Poh = 0; a.Pow = 0;
-      a.nphase = 0;
-    } else {
-      a.nphase = k;
-    }
     TORCH_CHECK(!empty, "conv_dgrad_bnred: stride-phase without taps");
     Tensor slab = torch::empty({mpa::igemm_bnred_slab_floats(N * H * W, C, std::max(a.nphase, 1))},
                                dy.options().dtype(torch::kFloat32));
@@ -315,26 +251,17 @@ static Tensor conv_dgrad_impl(Tensor dy, Tensor w, int64_t H, int64_t W, int64_t
     return dx;
   }
   if (sh == 1 && sw == 1) {
-    const mpa::PhaseDesc& d = a.ph[0];
-    a.M = d.M; a.oH = d.oH; a.oW = d.oW; a.T = d.T; a.Ktot = d.Ktot; a.Poh = 0; a.Pow = 0;
     Tensor ws;
     float* wsp = alloc_ws(ws, dy, mpa::igemm_ws_floats(a.M, a.N, a.Ktot));
     mpa::igemm_rows_dgrad(a, vw, wsp, cur_stream(), bkc);
   } else {
-    // phases with no taps (stride > kernel) leave their dx pixels zero (or, accumulating,
-    // untouched)
-    bool empty = false;
-    for (int i = 0; i < nph; ++i) empty |= a.ph[i].T == 0;
-    int k = 0;
-    for (int i = 0; i < nph; ++i)
-      if (a.ph[i].T > 0) a.ph[k++] = a.ph[i];
-    a.nphase = k;
     if (src2) {
       a.A2 = bp(src2->dy2);
       a.B2 = bp(src2->wt2);
-      a.ldb2 = src2->w2.size(1) * src2->w2.size(2) * K;
       if (!mpa::igemm_dgrad_src2_ok(a, vw, bkc)) return Tensor();  // caller runs them apart
     }
+    // phases with no taps (stride > kernel) leave their dx pixels zero (or, accumulating,
+    // untouched)
     if (empty && !acc) dx.zero_();
     mpa::igemm_rows_dgrad_phases(a, vw, cur_stream(), bkc);
   }
@@ -366,30 +293,22 @@ c10::optional<Tensor> conv_dgrad_res(Tensor dy, Tensor w, Tensor wt, int64_t H, 
   if (!(wt.defined() && wt.numel() == w.numel()) || vec_width(K) != 8 || vec_width(C) != 8 ||
       mpa::igemm_engine() < 1)
     return c10::nullopt;
-  if (P != H + 2 * ph - R + 1 || Q != W + 2 * pw - S + 1) return c10::nullopt;
+  if (P != mpa::conv_out_extent(H, R, 1, ph) || Q != mpa::conv_out_extent(W, S, 1, pw))
+    return c10::nullopt;
   if (C % 64 != 0) return c10::nullopt;  // (a column tile's 64 mask bits: one aligned 8-B load)
   const c10::OptionalDeviceGuard g(device_of(dy));
   Tensor dx = empty_like_shape(dy, {N, H, W, C}, torch::kBFloat16);
-  mpa::IGemmArgs a{};
-  a.A = bp(dy); a.aH = P; a.aW = Q; a.aC = K;
-  a.Uh = 1; a.Uw = 1; a.Oh = 0; a.Ow = 0;
-  a.B = bp(wt); a.N = C; a.RS = R * S; a.ldb = R * S * K; a.b_tapmap = 1;
+  mpa::IGemmArgs a;
+  bool empty;
+  const char* limit = mpa::conv_dgrad_args({N, (int)H, (int)W, C, K, R, S, 1, 1, (int)ph, (int)pw},
+                                           P, Q, true, nullptr, a, empty);
+  a.A = bp(dy);
+  a.B = bp(wt);
   a.C = dx.data_ptr(); a.ldc = C;
-  a.dH = H; a.dW = W; a.Uoh = 1; a.Uow = 1;
   a.beta = 1;
   a.ep_res = bp(res);
   a.ep_rmask = rmask.data_ptr<uint8_t>();
-  int T = 0;
-  for (int r = 0; r < R; ++r)
-    for (int s = 0; s < S; ++s) {
-      a.taps.dh[T] = ph - r;
-      a.taps.dw[T] = pw - s;
-      a.taps.bt[T] = r * S + s;
-      ++T;
-    }
-  a.T = T;
-  a.M = N * H * W; a.oH = H; a.oW = W; a.Ktot = T * K; a.Poh = 0; a.Pow = 0;
-  if (!mpa::conv3_halo_ok(a)) return c10::nullopt;
+  if (limit || !mpa::conv3_halo_ok(a)) return c10::nullopt;  // (the halo kernel is 3x3)
   mpa::igemm_rows_dgrad(a, 8, nullptr, cur_stream(), true);
   return dx;
 }
@@ -412,7 +331,8 @@ c10::optional<Tensor> conv_dgrad_pair(Tensor dy, Tensor w, Tensor wt, int64_t H,
   if (sh == 1 && sw == 1) return c10::nullopt;
   if (!(wt.defined() && wt.numel() == w.numel())) return c10::nullopt;
   // the two convs' output grids must coincide: P = (H + 2 ph - R) / sh + 1 for both
-  const int P2 = (H + 2 * ph2 - w2.size(1)) / sh + 1, Q2 = (W + 2 * pw2 - w2.size(2)) / sw + 1;
+  const int P2 = mpa::conv_out_extent(H, w2.size(1), sh, ph2);
+  const int Q2 = mpa::conv_out_extent(W, w2.size(2), sw, pw2);
   if (P2 != dy.size(1) || Q2 != dy.size(2)) return c10::nullopt;
   DgradSrc2 s2{dy2, w2, wt2, (int)ph2, (int)pw2};
   Tensor dx = conv_dgrad_impl(dy, w, H, W, sh, sw, ph, pw, wt, nullptr, accum, &s2);
@@ -470,16 +390,10 @@ Tensor conv_dgrad_bnred_gacc(Tensor dz, Tensor w, Tensor wt, Tensor zbuf, Tensor
     TORCH_CHECK(t->numel() >= Ci, "conv_dgrad_bnred_gacc: per-channel vector size");
   }
   const c10::OptionalDeviceGuard g(device_of(dz));
-  mpa::IGemmArgs a{};
-  a.A = bp(dz); a.aH = H; a.aW = W; a.aC = K;
-  a.oH = H; a.oW = W; a.M = N * H * W;
-  a.Uh = 1; a.Uw = 1; a.Oh = 0; a.Ow = 0;
-  a.T = 1;
-  a.taps.dh[0] = 0; a.taps.dw[0] = 0; a.taps.bt[0] = 0;
-  a.Ktot = K;
-  a.B = bp(wt); a.N = Ci; a.RS = 1; a.ldb = K; a.b_tapmap = 1;
+  mpa::IGemmArgs a = mpa::pointwise_args(N, H, W, K, Ci, K, true);
+  a.A = bp(dz);
+  a.B = bp(wt);
   a.C = G.data_ptr(); a.ldc = (int)zbuf.size(3);
-  a.dH = H; a.dW = W; a.Uoh = 1; a.Uow = 1; a.Poh = 0; a.Pow = 0;
   a.ep_z = bp(zbuf);
   a.ep_y = nullptr;
   a.ep_mean = mean.data_ptr<float>();
@@ -558,6 +472,14 @@ std::vector<Tensor> bn_bwd_apply(Tensor dy, Tensor x, Tensor y, Tensor mean, Ten
   return {dx, gout};
 }
 
+// the weight-gradient launch of the conv q whose dy is [N, P, Q, K] (slab: the caller's)
+static mpa::WGradArgs wgrad_args(const Tensor& dy, const Tensor& x, const Tensor& dw,
+                                 const mpa::ConvShape& q, int P, int Q, bool overwrite) {
+  mpa::WGradArgs a = mpa::conv_wgrad_args(q, P, Q, overwrite);
+  a.dy = bp(dy); a.x = bp(x); a.dw = dw.data_ptr<float>();
+  return a;
+}
+
 void conv_wgrad(Tensor dy, Tensor x, Tensor dw, int64_t sh, int64_t sw, int64_t ph, int64_t pw,
                 bool overwrite) {
   CHECK_ACT(dy);
@@ -571,13 +493,8 @@ void conv_wgrad(Tensor dy, Tensor x, Tensor dw, int64_t sh, int64_t sw, int64_t 
   const int R = dw.size(1), S = dw.size(2);
   TORCH_CHECK(dy.size(0) == N, "conv_wgrad: batch mismatch");
   const c10::OptionalDeviceGuard g(device_of(dy));
-  mpa::WGradArgs a{};
-  a.dy = bp(dy); a.x = bp(x); a.dw = dw.data_ptr<float>();
-  a.Kout = K; a.C = C; a.H = H; a.W = W; a.P = P; a.Q = Q; a.R = R; a.S = S;
-  a.sh = sh; a.sw = sw; a.ph = ph; a.pw = pw;
-  a.Mpix = N * P * Q;
-  a.Ncols = R * S * C;
-  a.overwrite = overwrite ? 1 : 0;
+  mpa::WGradArgs a = wgrad_args(
+      dy, x, dw, {N, H, W, C, K, R, S, (int)sh, (int)sw, (int)ph, (int)pw}, P, Q, overwrite);
   Tensor slab;
   a.slab = alloc_ws(slab, dy, mpa::igemm_wgrad_ws_floats(a.Kout, a.Ncols, a.Mpix));
   mpa::igemm_wgrad(a, vec_width(K), (C % 8 == 0) ? 8 : 1, cur_stream());
@@ -1036,15 +953,10 @@ Tensor maxpool_bn_bwd_sums(Tensor dp, Tensor zsel, Tensor mean, Tensor rstd, Ten
 static mpa::WGradArgs stem_pool_args(const Tensor& z, const Tensor& x, const Tensor& dw,
                                      int64_t sh, int64_t sw, int64_t ph, int64_t pw,
                                      bool overwrite) {
-  mpa::WGradArgs a{};
-  a.dy = bp(z); a.x = bp(x); a.dw = dw.data_ptr<float>();
-  a.Kout = z.size(3); a.C = x.size(3); a.H = x.size(1); a.W = x.size(2);
-  a.P = z.size(1); a.Q = z.size(2); a.R = dw.size(1); a.S = dw.size(2);
-  a.sh = sh; a.sw = sw; a.ph = ph; a.pw = pw;
-  a.Mpix = z.size(0) * a.P * a.Q;
-  a.Ncols = a.R * a.S * a.C;
-  a.overwrite = overwrite ? 1 : 0;
-  return a;
+  const mpa::ConvShape q{(int)z.size(0), (int)x.size(1), (int)x.size(2), (int)x.size(3),
+                         (int)z.size(3), (int)dw.size(1), (int)dw.size(2), (int)sh, (int)sw,
+                         (int)ph, (int)pw};
+  return wgrad_args(z, x, dw, q, (int)z.size(1), (int)z.size(2), overwrite);
 }
 
 static mpa::StemPoolArgs stem_pool_q(const Tensor& dp, const Tensor& idx, const Tensor& mean,
@@ -1164,16 +1076,11 @@ Tensor linear_fwd(Tensor x, Tensor w, Tensor bias, bool relu) {
   const int B = x.size(0), Cin = x.size(1), Cout = w.size(0);
   const c10::OptionalDeviceGuard g(device_of(x));
   Tensor y = empty_like_shape(x, {B, Cout}, torch::kBFloat16);
-  mpa::IGemmArgs a{};
-  a.A = bp(x); a.aH = 1; a.aW = 1; a.aC = Cin;
-  a.oH = 1; a.oW = 1; a.M = B;
-  a.Uh = 1; a.Uw = 1; a.Oh = 0; a.Ow = 0;
-  a.T = 1; a.taps.dh[0] = 0; a.taps.dw[0] = 0; a.taps.bt[0] = 0;
-  a.Ktot = Cin;
-  a.B = bp(w); a.N = Cout; a.RS = 1; a.ldb = Cin;
+  mpa::IGemmArgs a = mpa::pointwise_args(B, 1, 1, Cin, Cout, Cin);
+  a.A = bp(x);
+  a.B = bp(w);
   a.C = y.data_ptr(); a.ldc = Cout;
-  a.dH = 1; a.dW = 1; a.Uoh = 1; a.Uow = 1; a.Poh = 0; a.Pow = 0;
-  a.bias = fopt(bias); a.stats = nullptr; a.relu = relu ? 1 : 0;
+  a.bias = fopt(bias); a.relu = relu ? 1 : 0;
   Tensor ws;
   float* wsp = alloc_ws(ws, x, mpa::igemm_ws_floats(a.M, a.N, a.Ktot));
   mpa::igemm_rows(a, vec_width(Cin), wsp, nullptr, cur_stream());
@@ -1187,22 +1094,15 @@ Tensor linear_dgrad(Tensor dy, Tensor w, c10::optional<Tensor> wt_opt) {
   TORCH_CHECK(w.size(0) == Cout, "linear_dgrad: shapes");
   const c10::OptionalDeviceGuard g(device_of(dy));
   Tensor dx = empty_like_shape(dy, {B, Cin}, torch::kBFloat16);
-  mpa::IGemmArgs a{};
-  a.A = bp(dy); a.aH = 1; a.aW = 1; a.aC = Cout;
-  a.oH = 1; a.oW = 1; a.M = B;
-  a.Uh = 1; a.Uw = 1; a.Oh = 0; a.Ow = 0;
-  a.T = 1; a.taps.dh[0] = 0; a.taps.dw[0] = 0; a.taps.bt[0] = 0;
-  a.Ktot = Cout;
-  a.B = bp(w); a.N = Cin; a.RS = 1; a.ldb = Cin;
   const int vw = std::min(vec_width(Cout), vec_width(Cin));
   const bool bkc = wt_opt && wt_opt->defined() && wt_opt->numel() == w.numel() && vw == 8;
   if (bkc) {  // transposed weight [Cin][Cout]: B K-contiguous
     CHECK_ACT((*wt_opt));
-    a.B = bp(*wt_opt);
-    a.ldb = Cout;
   }
+  mpa::IGemmArgs a = mpa::pointwise_args(B, 1, 1, Cout, Cin, bkc ? Cout : Cin);
+  a.A = bp(dy);
+  a.B = bkc ? bp(*wt_opt) : bp(w);
   a.C = dx.data_ptr(); a.ldc = Cin;
-  a.dH = 1; a.dW = 1; a.Uoh = 1; a.Uow = 1; a.Poh = 0; a.Pow = 0;
   Tensor ws;
   float* wsp = alloc_ws(ws, dy, mpa::igemm_ws_floats(a.M, a.N, a.Ktot));
   mpa::igemm_rows_dgrad(a, vw, wsp, cur_stream(), bkc);
@@ -1217,12 +1117,7 @@ void linear_wgrad(Tensor dy, Tensor x, Tensor dw, bool overwrite) {
   const int B = dy.size(0), Cout = dy.size(1), Cin = x.size(1);
   TORCH_CHECK(dw.size(0) == Cout && dw.size(1) == Cin, "linear_wgrad: dw shape");
   const c10::OptionalDeviceGuard g(device_of(dy));
-  mpa::WGradArgs a{};
-  a.dy = bp(dy); a.x = bp(x); a.dw = dw.data_ptr<float>();
-  a.Kout = Cout; a.C = Cin; a.H = 1; a.W = 1; a.P = 1; a.Q = 1; a.R = 1; a.S = 1;
-  a.sh = 1; a.sw = 1; a.ph = 0; a.pw = 0;
-  a.Mpix = B; a.Ncols = Cin;
-  a.overwrite = overwrite ? 1 : 0;
+  mpa::WGradArgs a = wgrad_args(dy, x, dw, {B, 1, 1, Cin, Cout, 1, 1, 1, 1, 0, 0}, 1, 1, overwrite);
   Tensor slab;
   a.slab = alloc_ws(slab, dy, mpa::igemm_wgrad_ws_floats(a.Kout, a.Ncols, a.Mpix));
   mpa::igemm_wgrad(a, vec_width(Cout), (Cin % 8 == 0) ? 8 : 1, cur_stream());

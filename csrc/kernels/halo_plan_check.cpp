@@ -1,6 +1,7 @@
-// CPU check of the halo launch planner (halo_plan.h, the only project header included; any
-// host C++17 compiler, no GPU toolchain).  Run by tests/test_halo_plan_cpu.py, plain and
-// under AddressSanitizer + UndefinedBehaviorSanitizer.
+// CPU check of the halo launch planner (halo_plan.h, planning the launches conv_args.h
+// describes - the only project headers included; any host C++17 compiler, no GPU toolchain).
+// Run by tests/test_halo_plan_cpu.py, plain and under AddressSanitizer +
+// UndefinedBehaviorSanitizer.
 //
 //   halo_plan_check [key=value | fwd:... | wgrad:...] ...
 //
@@ -21,6 +22,7 @@
 #include <cstring>
 #include <string>
 
+#include "conv_args.h"
 #include "halo_plan.h"
 
 using namespace mpa;
@@ -45,34 +47,21 @@ static T* some() {  // a non-null operand (the planner only tests presence)
 
 // the launch the binding layer builds for the case; false: no such conv (valid, image < 3)
 static bool make_fwd(const FwdCase& q, IGemmArgs& a) {
-  a = IGemmArgs{};
   const bool valid = q.mode == 1 || q.mode == 2, dgrad = q.mode >= 2;
-  const int pad = valid ? 0 : 1, P = q.H + 2 * pad - 2, Q = q.W + 2 * pad - 2;
+  const int pad = valid ? 0 : 1;
+  const int P = conv_out_extent(q.H, 3, 1, pad), Q = conv_out_extent(q.W, 3, 1, pad);
+  a = IGemmArgs{};
   if (P <= 0 || Q <= 0) return false;
+  // (the GEMM's K channels c are the conv's input channels, or dy's for the dgrad from the
+  // transposed weight)
+  bool empty;
+  if (dgrad) conv_dgrad_args({q.batch, q.H, q.W, q.n, q.c, 3, 3, 1, 1, pad, pad}, P, Q, true,
+                             nullptr, a, empty);
+  else conv_fwd_args({q.batch, q.H, q.W, q.c, q.n, 3, 3, 1, 1, pad, pad}, false, a);
   a.A = some<const bf16_raw>();
   a.B = some<const bf16_raw>();
   a.C = some<void>();
-  a.aH = dgrad ? P : q.H;
-  a.aW = dgrad ? Q : q.W;
-  a.oH = dgrad ? q.H : P;
-  a.oW = dgrad ? q.W : Q;
-  a.aC = q.c;
-  a.M = q.batch * a.oH * a.oW;
-  a.Uh = a.Uw = a.Uoh = a.Uow = 1;
-  a.Oh = a.Ow = dgrad ? 0 : -pad;
-  a.T = a.RS = 9;
-  for (int r = 0; r < 3; ++r)
-    for (int s = 0; s < 3; ++s) {
-      a.taps.dh[3 * r + s] = (short)(dgrad ? pad - r : r);
-      a.taps.dw[3 * r + s] = (short)(dgrad ? pad - s : s);
-      a.taps.bt[3 * r + s] = (short)(3 * r + s);
-    }
-  a.Ktot = a.ldb = 9 * q.c;
-  a.b_tapmap = dgrad;
-  a.N = q.n;
   a.ldc = q.n + (q.wide ? 64 : 0);
-  a.dH = a.oH;
-  a.dW = a.oW;
   switch (q.flavour) {
     case 1: a.beta = 1; break;
     case 2: a.stats = some<float>(); break;
@@ -93,16 +82,11 @@ static bool make_fwd(const FwdCase& q, IGemmArgs& a) {
 }
 
 static bool make_wgrad(const WCase& q, WGradArgs& a) {
-  a = WGradArgs{};
+  a = conv_wgrad_args({q.batch, q.H, q.W, q.c, q.k, 3, 3, 1, 1, q.pad, q.pad},
+                      conv_out_extent(q.H, 3, 1, q.pad), conv_out_extent(q.W, 3, 1, q.pad), false);
   a.dy = a.x = some<const bf16_raw>();
   a.dw = a.slab = some<float>();
-  a.Kout = q.k; a.C = q.c; a.H = q.H; a.W = q.W;
-  a.P = q.H + 2 * q.pad - 2; a.Q = q.W + 2 * q.pad - 2;
-  a.R = a.S = 3; a.sh = a.sw = 1; a.ph = a.pw = q.pad;
-  if (a.P <= 0 || a.Q <= 0) return false;
-  a.Mpix = q.batch * a.P * a.Q;
-  a.Ncols = 9 * q.c;
-  return true;
+  return a.P > 0 && a.Q > 0;
 }
 
 // ------------------------------------------------------------------------ printing
