@@ -37,11 +37,16 @@
 
 namespace mpa {
 
+// Occupancy target (waves per SIMD) of the MFMA kernels in this file: 3 fits every tile in
+// <= 168 VGPRs with no spills (accumulators move from AGPRs to VGPRs); 4 (<= 128 VGPRs)
+// spills a few registers on the large tiles.
+constexpr int MFMA_OCC = 3;
+
 // ======================================================================================
 //  fwd / dgrad kernel
 // ======================================================================================
-template <int BM, int BN, int WM, int WN, int VW, bool BKC, bool SPLIT, int OCC>
-__global__ __launch_bounds__(256, OCC) void igemm_rows_kernel(IGemmArgs p) {
+template <int BM, int BN, int WM, int WN, int VW, bool BKC, bool SPLIT>
+__global__ __launch_bounds__(256, MFMA_OCC) void igemm_rows_kernel(IGemmArgs p) {
   constexpr int NA = BM / 64;                 // A chunks / thread
   constexpr int A_BYTES = BM * 64;
   constexpr int B_BYTES = BN * 64;
@@ -253,8 +258,8 @@ __global__ __launch_bounds__(256, OCC) void igemm_rows_kernel(IGemmArgs p) {
 // ======================================================================================
 //  wgrad kernel: dW[m = kout][n = (r,s,c)] += sum_pix dy[pix][m] * im2col(x)[pix][n]
 // ======================================================================================
-template <int BM, int BN, int WM, int WN, int VWA, int VWB, int OCC>
-__global__ __launch_bounds__(256, OCC) void igemm_wgrad_kernel(WGradArgs p) {
+template <int BM, int BN, int WM, int WN, int VWA, int VWB>
+__global__ __launch_bounds__(256, MFMA_OCC) void igemm_wgrad_kernel(WGradArgs p) {
   constexpr int A_BYTES = BK * BM * 2;
   constexpr int B_BYTES = BK * BN * 2;
   constexpr int STAGE = A_BYTES + B_BYTES;
@@ -528,52 +533,60 @@ __global__ __launch_bounds__(256) void splitk_finalize_kernel(
 }
 
 // ======================================================================================
-//  host-side launch logic
+//  host-side launch logic: the process's switches, the tile autotuner's state, and the
+//  launch of a plan.  What runs is decided in igemm_plan.h.
 // ======================================================================================
-// Occupancy target (waves per SIMD) for the MFMA kernels: 3 fits every tile in <= 168
-// VGPRs with no spills (accumulators move from AGPRs to VGPRs); 4 (<= 128 VGPRs) spills a
-// few registers on the large tiles.
-static int occ_target() { return 3; }
-
-// Staging engine for 16-B-granular operands: 0 = register-staged (this file),
-// 1 = tuned default: LDS-DMA (igemm_dma.hip) for the rows GEMMs (fwd / dgrad / linear);
-//     for wgrad the 8-wave generic DMA tile where it wins (wgrad_big), the incremental
-//     DMA kernel where it applies, register staging elsewhere,
-// 2 = LDS-DMA for every GEMM.  MPA_IGEMM_ENGINE=0|1|2 sets the start value;
-// igemm_set_engine switches at run time (A/B benchmarks, cross-checking tests).
-static int g_engine = -1;
-int igemm_engine() {
-  if (g_engine < 0) {
+// The one GemmSwitches object.  MPA_IGEMM_ENGINE=0|1|2 sets the engine's start value (read
+// at the first use), MPA_DMA_UNI=0 / MPA_KPAD=0 turn those paths off; igemm_set_engine,
+// igemm_set_dma_uni and igemm_force_tile switch at run time (A/B benchmarks, cross-checking
+// tests, tools/bench_kernels.py).
+static bool env_on(const char* e) { return !(e && e[0] == '0'); }  // (set to 0: off)
+static GemmSwitches g_sw = [] {
+  GemmSwitches sw;
+  sw.engine = -1;
+  sw.dma_uni = env_on(getenv("MPA_DMA_UNI"));
+  sw.kpad = env_on(getenv("MPA_KPAD"));
+  return sw;
+}();
+static const GemmSwitches& switches() {
+  if (g_sw.engine < 0) {
     const char* e = getenv("MPA_IGEMM_ENGINE");
-    g_engine = e ? std::min(2, std::max(0, atoi(e))) : 1;
+    g_sw.engine = e ? std::min(2, std::max(0, atoi(e))) : 1;
   }
-  return g_engine;
+  return g_sw;
 }
-void igemm_set_engine(int e) { g_engine = std::min(2, std::max(0, e)); }
-
-// Tile override for measurement (tools/bench_kernels.py): igemm_force_tile(BM, BN, splits);
-// zeros restore the heuristics.  Applies to both plans (rows and wgrad, BM x BN of the
-// respective GEMM) when the requested tile exists for the engine in use.
-static int g_force_bm = 0, g_force_bn = 0, g_force_splits = 0;
+int igemm_engine() { return switches().engine; }
+void igemm_set_engine(int e) { g_sw.engine = std::min(2, std::max(0, e)); }
+void igemm_set_dma_uni(int on) { g_sw.dma_uni = on != 0; }
+bool igemm_stap_ok() { return switches().dma_uni && switches().engine >= 1; }
 void igemm_force_tile(int bm, int bn, int splits) {
-  g_force_bm = bm; g_force_bn = bn; g_force_splits = splits;
+  g_sw.force_bm = bm; g_sw.force_bn = bn; g_sw.force_splits = splits;
+}
+
+int64_t igemm_ws_floats(int M, int N, int Ktot) { return rows_ws_floats(M, N, Ktot, switches()); }
+int64_t igemm_slab_floats(int M, int N) { return slab_floats(M, N); }
+int64_t igemm_bnred_slab_floats(int M, int N, int nphase) { return bnred_slab_floats(M, N, nphase); }
+int64_t igemm_wgrad_ws_floats(int Kout, int Ncols, int Mpix) {
+  int64_t best = conv3_halo_wgrad_ws_floats(Kout, Ncols);
+  if (Kout == 64 && Ncols == 224) best = std::max(best, stem_wgrad_ws_floats());
+  return std::max(best, wgrad_gemm_ws_floats(Kout, Ncols, Mpix, switches()));
+}
+bool igemm_dgrad_src2_ok(const IGemmArgs& a, int vw, bool bkc) {
+  return dgrad_src2_ok(a, vw, bkc, switches());
 }
 
 // ---------------------------------------------------------------------- tile autotuner
-// The static plans (rows_plan / wgrad_plan) were fitted on a few shapes and miss by 10-25 %
-// elsewhere (tools/bench_kernels.py sweep at batch 512: layer4's strided conv runs 24 %
-// faster on 256x128, layer2's strided wgrad 10 % faster on 128x256, layer3's 15 % faster on
-// 128x128).  Like cudnn.benchmark, the first launch of each GEMM shape on the LDS-DMA
-// engine times every eligible tile on scratch outputs (a warm-up run, then 3 timed ones)
-// and caches the fastest; later launches reuse it.  The sweep costs a few ms once per shape
-// (the warm-up steps of a training run), is skipped while a HIP graph is being captured
-// (the static plan runs then) and is off with MPA_TUNE=0.  Tiles never change a result's
-// summation order except through the split-K count, which candidates may not raise past
-// the caller's workspace.
-static bool g_tune = [] {
-  const char* e = getenv("MPA_TUNE");
-  return !(e && e[0] == '0');
-}();
+// The static plans (rows_tiling / wgrad_tiling) were fitted on a few shapes and miss by
+// 10-25 % elsewhere (tools/bench_kernels.py sweep at batch 512: layer4's strided conv runs
+// 24 % faster on 256x128, layer2's strided wgrad 10 % faster on 128x256, layer3's 15 %
+// faster on 128x128).  Like cudnn.benchmark, the first launch of each GEMM shape on the
+// LDS-DMA engine times every eligible tile on scratch outputs (a warm-up run, then 3 timed
+// ones) and caches the fastest; later launches reuse it.  The sweep costs a few ms once per
+// shape (the warm-up steps of a training run), is skipped while a HIP graph is being
+// captured (the static plan runs then) and is off with MPA_TUNE=0.  Tiles never change a
+// result's summation order except through the split-K count, which candidates may not
+// raise past the caller's workspace.
+static bool g_tune = env_on(getenv("MPA_TUNE"));
 void igemm_set_tune(int on) { g_tune = on != 0; }
 // Drain the whole device before timing a tuner candidate (single GPU: side / branch
 // streams may still run kernels whose overlap would bias the choice).  Off under data
@@ -582,11 +595,8 @@ void igemm_set_tune(int on) { g_tune = on != 0; }
 static bool g_tune_drain = true;
 void igemm_set_tune_drain(int on) { g_tune_drain = on != 0; }
 
-struct TunedTile {
-  int bm, bn;
-};
 static std::mutex g_tune_mu;
-static std::map<std::string, TunedTile> g_tuned;
+static std::map<std::string, TileSize> g_tuned;
 // held for a whole tuning pass (scratch growth + candidate launches + timing): a second
 // host thread tuning on the same device must not free the scratch buffer that this
 // thread's candidate kernels are still writing
@@ -640,17 +650,16 @@ static float time_launches(F&& fn, hipStream_t s) {
   return best;
 }
 
-static bool tuned_lookup(const std::string& key, int& bm, int& bn) {
+static bool tuned_lookup(const std::string& key, TileSize& t) {
   std::lock_guard<std::mutex> lock(g_tune_mu);
   auto it = g_tuned.find(key);
   if (it == g_tuned.end()) return false;
-  bm = it->second.bm;
-  bn = it->second.bn;
+  t = it->second;
   return true;
 }
-static void tuned_store(const std::string& key, int bm, int bn) {
+static void tuned_store(const std::string& key, TileSize t) {
   std::lock_guard<std::mutex> lock(g_tune_mu);
-  g_tuned[key] = TunedTile{bm, bn};
+  g_tuned[key] = t;
 }
 
 // number of tuned shapes and a readable dump ("key -> BMxBN" lines) for diagnostics
@@ -679,195 +688,129 @@ int igemm_tuned_load(const std::string& table, bool replace) {
     if (arrow == std::string::npos) continue;
     int bm = 0, bn = 0;
     if (sscanf(line.c_str() + arrow + 4, "%dx%d", &bm, &bn) != 2 || bm <= 0 || bn <= 0) continue;
-    g_tuned[line.substr(0, arrow)] = TunedTile{bm, bn};
+    g_tuned[line.substr(0, arrow)] = TileSize{bm, bn};
     ++n;
   }
   return n;
 }
 
-template <int BM, int BN, int WM, int WN, int VW, bool BKC, bool SPLIT>
-static void launch_rows(const IGemmArgs& a0, int splits, hipStream_t s) {
-  IGemmArgs a = a0;
-  igemm_set_fastdiv(a);
-  dim3 grid(a.tiles_total, 1, splits);
-  const int o = occ_target();
-  if (o == 4)
-    hipLaunchKernelGGL((igemm_rows_kernel<BM, BN, WM, WN, VW, BKC, SPLIT, 4>), grid, dim3(256), 0,
-                       s, a);
-  else if (o == 2)
-    hipLaunchKernelGGL((igemm_rows_kernel<BM, BN, WM, WN, VW, BKC, SPLIT, 2>), grid, dim3(256), 0,
-                       s, a);
-  else
-    hipLaunchKernelGGL((igemm_rows_kernel<BM, BN, WM, WN, VW, BKC, SPLIT, 3>), grid, dim3(256), 0,
-                       s, a);
+// The autotuned tile of the GEMM shape `make_key()` names (zeros: keep the heuristic).
+// `plan(c, run)` plans candidate c on scratch outputs (tune_scratch) and fills the Run that
+// `launch(run)` then launches; Skip: the candidate is not eligible (its tile does not exist
+// for the launch, or its split slab would not fit the caller's workspace); Stop: no scratch
+// memory - the pass is abandoned, nothing is stored and the heuristic tile runs.
+enum class Cand { Skip, Stop, Ready };
+struct RowsRun {
+  RowsLaunch p;
+  IGemmArgs a;
+  float *ws, *slab;
+};
+struct WGradRun {
+  WGradLaunch p;
+  WGradArgs a;
+};
+template <class Run, class Key, int N, class Plan, class Launch>
+static TileSize tuned_tile(Key&& make_key, const TileSize (&cands)[N], hipStream_t s, Plan&& plan,
+                           Launch&& launch) {
+  TileSize best_tile{0, 0};
+  if (!g_tune || deterministic() || (g_sw.force_bm && g_sw.force_bn) || stream_capturing(s))
+    return best_tile;
+  const std::string key = make_key();
+  if (tuned_lookup(key, best_tile)) return best_tile;
+  std::lock_guard<std::mutex> pass(g_tune_pass_mu);
+  if (tuned_lookup(key, best_tile)) return best_tile;  // tuned by another thread meanwhile
+  float best = 1e30f;
+  Run run{};
+  for (const TileSize& c : cands) {
+    const Cand r = plan(c, run);
+    if (r == Cand::Stop) return TileSize{0, 0};
+    if (r == Cand::Skip) continue;
+    const float t = time_launches([&] { launch(run); }, s);
+    if (t < best) { best = t; best_tile = c; }
+  }
+  if (best_tile.bm) tuned_store(key, best_tile);
+  return best_tile;
+}
+
+// ------------------------------------------------------------------------ rows launches
+[[noreturn]] void no_kernel(const char* what, int bm, int bn, int wm, int wn, int x, int y) {
+  fprintf(stderr, "%s: no kernel for the planned tile %dx%d (%dx%d waves; %d, %d)\n", what, bm, bn,
+          wm, wn, x, y);
+  abort();
 }
 
 template <int BM, int BN, int WM, int WN, bool BKC, bool SPLIT>
-static void dispatch_vw(const IGemmArgs& a, int vw, int splits, hipStream_t s) {
-  if (vw == 8) launch_rows<BM, BN, WM, WN, 8, BKC, SPLIT>(a, splits, s);
-  else if (vw == 4) launch_rows<BM, BN, WM, WN, 4, BKC, SPLIT>(a, splits, s);
-  else launch_rows<BM, BN, WM, WN, 1, BKC, SPLIT>(a, splits, s);
-}
-
-template <int BM, int BN, int WM, int WN, bool BKC>
-static void dispatch_split(const IGemmArgs& a, int vw, int splits, hipStream_t s) {
-  if (splits > 1) dispatch_vw<BM, BN, WM, WN, BKC, true>(a, vw, splits, s);
-  else dispatch_vw<BM, BN, WM, WN, BKC, false>(a, vw, splits, s);
-}
-
-static int choose_bn(int N) {
-  if (N <= 32) return 32;
-  if (N <= 64 || (N % 128 != 0 && N % 64 == 0 && N < 256)) return 64;
-  return 128;
-}
-
-// Split-K for grids smaller than the chip (< 256 tiles): each split stores its partial
-// tile with plain 16-B stores into a [splits][M][N] fp32 slab and splitk_finalize sums
-// them (+bias, ReLU, bf16, BN statistics) - no atomics.  Slab traffic is
-// 2 * splits * M * N * 4 bytes, small next to the GEMM for these deep-K shapes.
-static int choose_splits(int tiles, int ktiles) {
-  if (tiles >= 256 || ktiles < 16) return 1;
-  int s = (512 + tiles - 1) / tiles;
-  s = std::min(s, ktiles / 8);
-  s = std::min(s, 64);
-  return std::max(s, 1);
-}
-
-static void finish_split_plan(int ktiles, int& splits, int& per_split) {
-  per_split = ktiles > 0 ? (ktiles + splits - 1) / splits : 1;
-  splits = ktiles > 0 ? (ktiles + per_split - 1) / per_split : 1;
-}
-
-// dma: the LDS-DMA engine will run it (adds the 8-wave 256x128 / 256x256 tiles, reachable
-// through igemm_force_tile; tools/bench_kernels.py sweep measures them slower than 128x128
-// on every ResNet layer: they leave the grid under one block per CU or force split-K,
-// whose fp32 partial slab costs more than the tile saves).
-static bool rows_tile_ok(int bm, int bn, bool dma) {
-  const bool ok_reg = (bm == 128 && bn == 128) || (bm == 256 && bn == 64) || (bm == 128 && bn == 32);
-  const bool ok_dma = ok_reg || (bm == 256 && (bn == 256 || bn == 128)) || (bm == 128 && bn == 64);
-  return dma ? ok_dma : ok_reg;
-}
-
-// tbm / tbn: a tile chosen by the autotuner (0: the heuristic); igemm_force_tile wins
-static void rows_plan(IGemmArgs& a, int& BM, int& BN, int& splits, bool allow_split, bool dma,
-                      int tbm = 0, int tbn = 0) {
-  BN = choose_bn(a.N);
-  // 64-wide GEMMs: the DMA engine's 128x64 tile (36 KiB ring, 4 blocks/CU) beats 256x64
-  // (60 KiB, 2 blocks/CU) on every ResNet-18 64-channel layer by 8-20 % (tile sweep)
-  BM = (BN == 64 && !dma) ? 256 : 128;
-  const int ktiles = (a.Ktot + BK - 1) / BK;
-  if (tbm && tbn && rows_tile_ok(tbm, tbn, dma)) { BM = tbm; BN = tbn; }
-  if (g_force_bm && g_force_bn && rows_tile_ok(g_force_bm, g_force_bn, dma)) {
-    BM = g_force_bm;
-    BN = g_force_bn;
+static void launch_rows_reg(const RowsLaunch& p, const IGemmArgs& a, hipStream_t s) {
+  const dim3 grid(p.grid_x, 1, p.splits), block(p.block);
+  switch (p.VW) {
+    case 8: hipLaunchKernelGGL((igemm_rows_kernel<BM, BN, WM, WN, 8, BKC, SPLIT>), grid, block, 0, s, a); break;
+    case 4: hipLaunchKernelGGL((igemm_rows_kernel<BM, BN, WM, WN, 4, BKC, SPLIT>), grid, block, 0, s, a); break;
+    default: hipLaunchKernelGGL((igemm_rows_kernel<BM, BN, WM, WN, 1, BKC, SPLIT>), grid, block, 0, s, a);
   }
-  a.tiles_n = (a.N + BN - 1) / BN;
-  const int tiles_m = (a.M + BM - 1) / BM;
-  a.tiles_total = tiles_m * a.tiles_n;
-  splits = allow_split ? choose_splits(a.tiles_total, ktiles) : 1;
-  if (allow_split && g_force_splits > 0) splits = std::min(g_force_splits, std::max(ktiles, 1));
-  finish_split_plan(ktiles, splits, a.ktiles_per_split);
 }
 
-static bool use_dma(int vw) { return vw == 8 && igemm_engine() >= 1; }
-
-int64_t igemm_ws_floats(int M, int N, int Ktot) {
-  int64_t best = 0;
-  for (int dma = 0; dma < 2; ++dma) {  // sized for whichever engine ends up running it
-    IGemmArgs a{};
-    a.M = M; a.N = N; a.Ktot = Ktot;
-    int BM, BN, splits;
-    rows_plan(a, BM, BN, splits, true, dma == 1);
-    if (splits > 1) best = std::max(best, (int64_t)splits * M * N);
+template <int BM, int BN, int WM, int WN>
+static void launch_rows_reg_tile(const RowsLaunch& p, const IGemmArgs& a, hipStream_t s) {
+  if (p.BKC) {
+    if (p.SPLIT) launch_rows_reg<BM, BN, WM, WN, true, true>(p, a, s);
+    else launch_rows_reg<BM, BN, WM, WN, true, false>(p, a, s);
+  } else {
+    if (p.SPLIT) launch_rows_reg<BM, BN, WM, WN, false, true>(p, a, s);
+    else launch_rows_reg<BM, BN, WM, WN, false, false>(p, a, s);
   }
-  return best;
 }
 
-// statistics slab rows: one per 128-row M-tile (the smallest BM of any plan), per halo /
-// stem block or per splitk_finalize block row (<= slab_rows_max), then the [2][N] sums
-static int64_t slab_rows_max(int M) {
-  return std::max<int64_t>((M + 127) / 128, std::max(64, HALO_MAX_ROWS));
-}
-
-int64_t igemm_slab_floats(int M, int N) { return slab_rows_max(M) * 2 * N + 2 * N; }
-
-static void rows_run_plan(IGemmArgs a, bool bkc, int vw, float* ws, float* slab, hipStream_t s,
-                          int tbm, int tbn);
-
-static std::string rows_key(const IGemmArgs& a, bool bkc, bool split) {
-  char k[256];
-  snprintf(k, sizeof k, "rows%d%d M%d N%d K%d a%dx%dx%d o%dx%d U%d,%d O%d,%d T%d s%d b%d r%d p%d",
-           (int)bkc, (int)split, a.M, a.N, a.Ktot, a.aH, a.aW, a.aC, a.oH, a.oW, a.Uh, a.Uw,
-           a.Oh, a.Ow, a.T, a.stap, a.beta, a.relu, a.nphase);
-  std::string key(k);
-  for (int i = 0; i < a.nphase; ++i)
-    key += " " + std::to_string(a.ph[i].M) + "," + std::to_string(a.ph[i].Ktot);
-  return key;
-}
-
-static const int kRowsCands[][2] = {{128, 128}, {256, 128}, {128, 64}, {256, 64}, {128, 32},
-                                    {256, 256}};
-
-// The 8-wave 256 x 256 rows tile is not an autotuner candidate: same-box A/B, round 3 -
-// ResNet-18 b1024 47.73k/47.89k vs 47.67k/47.85k img/s, Inception 7.24k vs 7.26k,
-// ResNet-34 25.35k vs 25.39k (noise) - for a longer first-step tuning pass.
-
-static bool rows_cand_ok(int bm, int bn, int N) {
-  if (bm == 256 && bn == 256) return false;
-  if (bn == 128 && N <= 64) return false;  // half-empty tiles
-  if (bn == 64 && (N <= 32 || N > 1024)) return false;
-  if (bn == 32 && N > 32) return false;
-  return true;
-}
-
-// autotuned tile of a rows GEMM (fills tbm / tbn; leaves them 0 to keep the heuristic)
-static void tuned_rows_tile(const IGemmArgs& a, bool bkc, int vw, bool allow_split, hipStream_t s,
-                            int& tbm, int& tbn) {
-  if (!g_tune || deterministic() || (g_force_bm && g_force_bn) || a.M <= 0 || stream_capturing(s))
-    return;
-  const std::string key = rows_key(a, bkc, allow_split);
-  if (tuned_lookup(key, tbm, tbn)) return;
-  std::lock_guard<std::mutex> pass(g_tune_pass_mu);
-  if (tuned_lookup(key, tbm, tbn)) return;  // tuned by another thread meanwhile
-  const int64_t ws_cap = allow_split ? igemm_ws_floats(a.M, a.N, a.Ktot) : 0;
-  const int64_t cbytes = ((int64_t)a.M * std::max(a.ldc, a.N) * 2 + 255) / 256 * 256;
-  const int64_t sbytes = (igemm_slab_floats(a.M, a.N) + 2 * a.N) * 4;
-  float best = 1e30f;
-  int bbm = 0, bbn = 0;
-  for (const auto& c : kRowsCands) {
-    if (!rows_cand_ok(c[0], c[1], a.N)) continue;
-    IGemmArgs b = a;
-    int BM, BN, sp;
-    rows_plan(b, BM, BN, sp, allow_split, true, c[0], c[1]);
-    if (BM != c[0] || BN != c[1]) continue;
-    if (sp > 1 && (int64_t)sp * a.M * a.N > ws_cap) continue;
-    const int64_t wbytes = sp > 1 ? (int64_t)sp * a.M * a.N * 4 : 0;
-    char* scr = tune_scratch(cbytes + sbytes + wbytes + 512);
-    if (!scr) return;
-    b = a;
-    b.C = scr;
-    float* slab = (float*)(scr + cbytes);
-    if (a.stats) b.stats = slab + igemm_slab_floats(a.M, a.N);  // [2][N] after the slab
-    b.stats_ld = 0;
-    float* ws = sp > 1 ? (float*)(scr + cbytes + sbytes) : nullptr;
-    if (!allow_split) ws = nullptr;
-    else if (!ws) ws = (float*)(scr + cbytes + sbytes);  // (unused: no split)
-    const float t = time_launches([&] { rows_run_plan(b, bkc, vw, ws, slab, s, c[0], c[1]); }, s);
-    if (t < best) { best = t; bbm = c[0]; bbn = c[1]; }
+// register family: the rows of kRowsRegTiles
+static void igemm_rows_reg(const RowsLaunch& p, const IGemmArgs& a0, hipStream_t s) {
+  IGemmArgs a = a0;
+  igemm_set_fastdiv(a);
+  switch (p.BM * 1000 + p.BN) {
+    case 128128: launch_rows_reg_tile<128, 128, 2, 2>(p, a, s); break;
+    case 256064: launch_rows_reg_tile<256, 64, 4, 1>(p, a, s); break;
+    case 128032: launch_rows_reg_tile<128, 32, 4, 1>(p, a, s); break;
+    default: no_kernel("igemm_rows_reg", p.BM, p.BN, p.WM, p.WN, p.VW, 0);
   }
-  if (!bbm) return;
-  tuned_store(key, bbm, bbn);
-  tbm = bbm;
-  tbn = bbn;
 }
 
-static const bool g_kpad = [] {
-  const char* e = getenv("MPA_KPAD");
-  return !(e && e[0] == '0');
-}();
+// the planned kernel alone (the plan's argument fields set)
+static void launch_rows_kernel(const RowsLaunch& p, IGemmArgs a, hipStream_t s) {
+  p.apply(a);
+  if (p.family == RowsFamily::Reg) igemm_rows_reg(p, a, s);
+  else igemm_rows_dma(p, a, s);
+}
+
+// One planned rows GEMM with its follow-ups.  `a.stats` (if set) receives the finalized
+// per-column statistics [mean(N), var(N)] (biased variance, from sums shifted by
+// a.stats_shift); `slab` is a workspace of igemm_slab_floats(M, N) floats, its rows first,
+// then the [2][N] sums; `ws` holds the split-K partials when the plan splits.
+static void launch_rows(const RowsLaunch& p, IGemmArgs a, float* ws, float* slab, hipStream_t s) {
+  void* final_out = a.C;
+  float* stats = a.stats;
+  float* sums = stats ? slab + slab_rows_max(a.M) * 2 * a.N : nullptr;
+  a.stats = stats ? slab : nullptr;
+  a.stats_sums = sums;
+  if (p.to_ws) {
+    a.C = ws;
+    a.ldc = a.N;
+  }
+  launch_rows_kernel(p, a, s);
+  if (p.fin_cw) {
+    const dim3 grid(p.fin_gx, p.fin_gy);
+    if (p.fin_cw == 32)
+      hipLaunchKernelGGL(splitk_finalize_kernel<32>, grid, dim3(256), 0, s, ws, p.splits,
+                         (bf16_t*)final_out, a.M, a.N, a.bias, a.relu,
+                         stats ? slab : (float*)nullptr, a.stats_shift, sums, a.beta);
+    else
+      hipLaunchKernelGGL(splitk_finalize_kernel<64>, grid, dim3(256), 0, s, ws, p.splits,
+                         (bf16_t*)final_out, a.M, a.N, a.bias, a.relu,
+                         stats ? slab : (float*)nullptr, a.stats_shift, sums, a.beta);
+  }
+  if (stats) slab_stats(slab, p.slab_rows, a.N, a.stats_shift, a.M, sums, stats, s, a.stats_ld);
+}
 
 static void run_rows(IGemmArgs a, bool bkc, int vw, float* ws, float* slab, hipStream_t s) {
-  const bool dma = use_dma(vw);
+  const GemmSwitches& sw = switches();
+  const bool dma = rows_dma(vw, sw);
   if (dma && bkc && conv_stem_ok(a)) {  // 7x7 pixel-pair stem: row-staged direct conv
     float* stats = a.stats;
     float* sums = stats ? slab + slab_rows_max(a.M) * 2 * a.N : nullptr;
@@ -886,74 +829,40 @@ static void run_rows(IGemmArgs a, bool bkc, int vw, float* ws, float* slab, hipS
     if (stats) slab_stats(slab, rows, a.N, a.stats_shift, a.M, sums, stats, s, a.stats_ld);
     return;
   }
-  // 16-B but not 32-granular channel counts (Inception 48 / 80): the uniform-tap kernel
-  // with each tap's K padded to 32 (MPA_KPAD=0: the generic gather kernel); no split-K (the
-  // caller's workspace was sized for the unpadded K)
-  if (dma && g_kpad && igemm_rows_kpad_ok(a, bkc)) {
-    a.Ktot = a.T * ((a.aC + BK - 1) / BK) * BK;
-    a.kpad = 1;
-    ws = nullptr;
-  }
-  int tbm = 0, tbn = 0;
-  if (dma) tuned_rows_tile(a, bkc, vw, ws != nullptr, s, tbm, tbn);
-  rows_run_plan(a, bkc, vw, ws, slab, s, tbm, tbn);
+  // (a padded-K launch never splits: the caller's workspace was sized for the unpadded K)
+  const int kp = rows_kpad_ktot(a, bkc, vw, sw);
+  const int Ktot = kp ? kp : a.Ktot;
+  if (kp) ws = nullptr;
+  const bool allow_split = ws != nullptr;
+  TileSize tuned{0, 0};
+  if (dma && a.M > 0)
+    tuned = tuned_tile<RowsRun>(
+        [&] { return rows_key(a, Ktot, bkc, allow_split); }, kRowsCands, s,
+        [&](TileSize c, RowsRun& r) {
+          if (!rows_cand_ok(c, a.N)) return Cand::Skip;
+          r.p = plan_rows(a, bkc, vw, allow_split, sw, c);
+          if (r.p.BM != c.bm || r.p.BN != c.bn) return Cand::Skip;
+          const int64_t ws_cap = allow_split ? rows_ws_floats(a.M, a.N, Ktot, sw) : 0;
+          if (r.p.splits > 1 && (int64_t)r.p.splits * a.M * a.N > ws_cap) return Cand::Skip;
+          const int64_t cbytes = ((int64_t)a.M * std::max(a.ldc, a.N) * 2 + 255) / 256 * 256;
+          const int64_t sbytes = (slab_floats(a.M, a.N) + 2 * a.N) * 4;
+          const int64_t wbytes = r.p.splits > 1 ? (int64_t)r.p.splits * a.M * a.N * 4 : 0;
+          char* scr = tune_scratch(cbytes + sbytes + wbytes + 512);
+          if (!scr) return Cand::Stop;
+          r.a = a;
+          r.a.C = scr;
+          r.slab = (float*)(scr + cbytes);
+          if (a.stats) r.a.stats = r.slab + slab_floats(a.M, a.N);  // [2][N] after the slab
+          r.a.stats_ld = 0;
+          r.ws = allow_split ? (float*)(scr + cbytes + sbytes) : nullptr;
+          return Cand::Ready;
+        },
+        [&](const RowsRun& r) { launch_rows(r.p, r.a, r.ws, r.slab, s); });
+  launch_rows(plan_rows(a, bkc, vw, allow_split, sw, tuned), a, ws, slab, s);
 }
 
-// the GEMM part of run_rows for a given (tuned) tile
-static void rows_run_plan(IGemmArgs a, bool bkc, int vw, float* ws, float* slab, hipStream_t s,
-                          int tbm, int tbn) {
-  int BM, BN, splits;
-  const bool dma = use_dma(vw);
-  rows_plan(a, BM, BN, splits, ws != nullptr, dma, tbm, tbn);
-  const int tiles_m = (a.M + BM - 1) / BM;
-  void* final_out = a.C;
-  float* stats = a.stats;
-  float* sums = stats ? slab + slab_rows_max(a.M) * 2 * a.N : nullptr;
-  a.stats = stats ? slab : nullptr;
-  a.stats_sums = sums;
-  if (splits > 1) {
-    a.C = ws;
-    a.ldc = a.N;
-  }
-  if (dma && igemm_rows_dma(a, BM, BN, bkc, splits, s)) {
-    // LDS-DMA engine (igemm_dma.hip)
-  } else if (a.kpad) {  // (unreachable: every planned tile has a kernel)
-    fprintf(stderr, "rows_run_plan: padded-K launch without an LDS-DMA kernel\n");
-    abort();
-  } else if (bkc) {
-    if (BN == 128) dispatch_split<128, 128, 2, 2, true>(a, vw, splits, s);
-    else if (BN == 64) dispatch_split<256, 64, 4, 1, true>(a, vw, splits, s);
-    else dispatch_split<128, 32, 4, 1, true>(a, vw, splits, s);
-  } else {
-    if (BN == 128) dispatch_split<128, 128, 2, 2, false>(a, vw, splits, s);
-    else if (BN == 64) dispatch_split<256, 64, 4, 1, false>(a, vw, splits, s);
-    else dispatch_split<128, 32, 4, 1, false>(a, vw, splits, s);
-  }
-  int slab_rows = tiles_m;
-  if (splits > 1) {
-    // ~512+ blocks (two rows in flight per thread), at most one slab row per block row
-    const int cw = a.N <= 32 ? 32 : 64, rp = 256 / cw, gx = (a.N + cw - 1) / cw;
-    const int gy = (int)std::min<int64_t>(slab_rows_max(a.M),
-                                          std::max(1, std::min((a.M + 2 * rp - 1) / (2 * rp),
-                                                               (1024 + gx - 1) / gx)));
-    dim3 grid(gx, gy);
-    if (cw == 32)
-      hipLaunchKernelGGL(splitk_finalize_kernel<32>, grid, dim3(256), 0, s, ws, splits,
-                         (bf16_t*)final_out, a.M, a.N, a.bias, a.relu,
-                         stats ? slab : (float*)nullptr, a.stats_shift, sums, a.beta);
-    else
-      hipLaunchKernelGGL(splitk_finalize_kernel<64>, grid, dim3(256), 0, s, ws, splits,
-                         (bf16_t*)final_out, a.M, a.N, a.bias, a.relu,
-                         stats ? slab : (float*)nullptr, a.stats_shift, sums, a.beta);
-    slab_rows = gy;
-  }
-  if (stats) slab_stats(slab, slab_rows, a.N, a.stats_shift, a.M, sums, stats, s, a.stats_ld);
-}
-
-// `a.stats` (if set) receives the finalized per-column statistics [mean(N), var(N)]
-// (biased variance, from sums shifted by a.stats_shift); `slab` is a workspace of
-// igemm_slab_floats(M, N) floats; `ws` holds igemm_ws_floats(M, N, Ktot) floats for the
-// split-K partials (nullptr disables split-K, e.g. for strided output mappings).
+// `ws` holds igemm_ws_floats(M, N, Ktot) floats for the split-K partials (nullptr disables
+// split-K, e.g. for strided output mappings); `slab`: see launch_rows.
 void igemm_rows(IGemmArgs a, int vw, float* ws, float* slab, hipStream_t s) {
   run_rows(a, true, vw, ws, slab, s);
 }
@@ -965,36 +874,6 @@ void igemm_rows_dgrad(IGemmArgs a, int vw, float* ws, hipStream_t s, bool bkc) {
 }
 
 // dgrad + fused BN-backward reduction (LDS-DMA engine only: one launch, dense slab rows)
-int64_t igemm_bnred_slab_floats(int M, int N, int nphase) {
-  const int64_t rows = std::max<int64_t>((int64_t)((M + 127) / 128 + 1) * std::max(nphase, 1),
-                                         HALO_MAX_ROWS);
-  return rows * 2 * N;
-}
-
-// tile plan of a merged stride-phase launch; returns the number of (phase, m-tile) rows
-static int plan_phases(IGemmArgs& a, int& BM, int& BN, int tbm = 0, int tbn = 0) {
-  IGemmArgs probe = a;
-  probe.M = 0;
-  probe.Ktot = 0;
-  for (int i = 0; i < a.nphase; ++i) {
-    probe.M = std::max(probe.M, a.ph[i].M);
-    probe.Ktot = std::max(probe.Ktot, a.ph[i].Ktot);
-  }
-  int splits;
-  rows_plan(probe, BM, BN, splits, false, true, tbm, tbn);
-  a.tiles_n = (a.N + BN - 1) / BN;
-  int most = 0, rows = 0;
-  for (int i = 0; i < a.nphase; ++i) {
-    const int mts = (a.ph[i].M + BM - 1) / BM;
-    a.ph[i].tiles = mts * a.tiles_n;
-    most = std::max(most, a.ph[i].tiles);
-    rows += mts;
-  }
-  a.tiles_total = most * a.nphase;
-  a.ktiles_per_split = 1 << 30;
-  return rows;
-}
-
 void igemm_rows_dgrad_bnred(IGemmArgs a, int vw, bool bkc, float* slab, float* sums,
                             hipStream_t s) {
   (void)vw;  // callers guarantee 16-B granular operands (LDS-DMA engine)
@@ -1004,75 +883,57 @@ void igemm_rows_dgrad_bnred(IGemmArgs a, int vw, bool bkc, float* slab, float* s
   a.ep_bnred = 1;
   a.stats = slab;
   a.stats_sums = sums;
-  int BM, BN, rows;
   if (a.nphase == 0 && bkc) {
     IGemmArgs t = a;
     if (t.ep_gamma && t.ep_beta) t.ep_y = nullptr;  // the halo kernel's z-mask form
     const HaloLaunch halo = conv3_halo_plan(t);
     if (halo.kind != HaloKind::None) {
-      rows = conv3_halo(t, halo, s);
+      const int rows = conv3_halo(t, halo, s);
       slab_reduce(slab, rows, 2 * a.N, sums, false, s);
       return;
     }
   }
-  if (a.nphase > 0) {
-    rows = plan_phases(a, BM, BN);
-  } else {
-    int splits;
-    rows_plan(a, BM, BN, splits, false, true);
-    rows = (a.M + BM - 1) / BM;
-  }
-  igemm_rows_dma(a, BM, BN, bkc, 1, s);
-  slab_reduce(slab, rows, 2 * a.N, sums, false, s);
+  const RowsLaunch p = a.nphase > 0
+                           ? plan_rows_phases(a, bkc, switches(), TileSize{0, 0})
+                           : plan_rows_on(a, bkc, 8, false, true, false, switches(), TileSize{0, 0});
+  launch_rows_kernel(p, a, s);
+  slab_reduce(slab, p.slab_rows, 2 * a.N, sums, false, s);
 }
 
 // All stride phases in ONE launch on the LDS-DMA engine: a stride-2 conv's dgrad is 4
 // GEMMs of a quarter of the pixels each; launched separately each fills a fraction of the
 // 256 CUs (ResNet-18 layer4 at batch 256: 196 tiles per phase), merged they fill it.
-bool igemm_dgrad_src2_ok(const IGemmArgs& a, int vw, bool bkc) {
-  return use_dma(vw) && a.nphase > 0 && a.nphase <= MAXPH && igemm_rows_uni_src2_ok(a, bkc);
-}
-
 void igemm_rows_dgrad_phases(IGemmArgs a, int vw, hipStream_t s, bool bkc) {
+  const GemmSwitches& sw = switches();
   a.stats = nullptr;
   a.bias = nullptr;
   if (a.nphase <= 0) return;
-  if (a.A2 && !igemm_dgrad_src2_ok(a, vw, bkc)) {
+  if (a.A2 && !dgrad_src2_ok(a, vw, bkc, sw)) {
     fprintf(stderr, "igemm_rows_dgrad_phases: second source on an ineligible launch\n");
     abort();
   }
-  if (use_dma(vw) && a.nphase <= MAXPH) {
-    int tbm = 0, tbn = 0;
-    if (g_tune && !deterministic() && !(g_force_bm && g_force_bn) && !stream_capturing(s)) {
-      const std::string key = rows_key(a, bkc, false);
-      std::unique_lock<std::mutex> pass(g_tune_pass_mu, std::defer_lock);
-      if (!tuned_lookup(key, tbm, tbn) && (pass.lock(), !tuned_lookup(key, tbm, tbn))) {
-        // time the merged launch per candidate tile
-        const int64_t hw0 = std::max(1, a.ph[0].oH * a.ph[0].oW);
-        const int64_t rows = (a.ph[0].M + hw0 - 1) / hw0 * a.dH * a.dW;  // dx pixels
-        const int64_t cbytes = rows * std::max(a.ldc, a.N) * 2;
-        char* scr = tune_scratch(cbytes + 256);
-        float best = 1e30f;
-        for (const auto& c : kRowsCands) {
-          if (!scr || !rows_cand_ok(c[0], c[1], a.N)) continue;
-          IGemmArgs b = a;
-          int BM, BN;
-          plan_phases(b, BM, BN, c[0], c[1]);
-          if (BM != c[0] || BN != c[1] || b.tiles_total <= 0) continue;
-          b.C = scr;
-          const float t = time_launches([&] { igemm_rows_dma(b, BM, BN, bkc, 1, s); }, s);
-          if (t < best) { best = t; tbm = c[0]; tbn = c[1]; }
-        }
-        if (tbm) tuned_store(key, tbm, tbn);
-      }
+  if (rows_dma(vw, sw) && a.nphase <= MAXPH) {
+    // the tuner times the merged launch per candidate tile
+    const TileSize tuned = tuned_tile<RowsRun>(
+        [&] { return rows_key(a, a.Ktot, bkc, false); }, kRowsCands, s,
+        [&](TileSize c, RowsRun& r) {
+          if (!rows_cand_ok(c, a.N)) return Cand::Skip;
+          r.p = plan_rows_phases(a, bkc, sw, c);
+          if (r.p.BM != c.bm || r.p.BN != c.bn || r.p.tiles_total <= 0) return Cand::Skip;
+          const int64_t hw0 = std::max(1, a.ph[0].oH * a.ph[0].oW);
+          const int64_t rows = (a.ph[0].M + hw0 - 1) / hw0 * a.dH * a.dW;  // dx pixels
+          char* scr = tune_scratch(rows * std::max(a.ldc, a.N) * 2 + 256);
+          if (!scr) return Cand::Stop;
+          r.a = a;
+          r.a.C = scr;
+          return Cand::Ready;
+        },
+        [&](const RowsRun& r) { launch_rows_kernel(r.p, r.a, s); });
+    const RowsLaunch p = plan_rows_phases(a, bkc, sw, tuned);
+    if (p.tiles_total > 0) {
+      launch_rows_kernel(p, a, s);
+      return;
     }
-    int BM, BN;
-    plan_phases(a, BM, BN, tbm, tbn);
-    if (a.tiles_total > 0 && igemm_rows_dma(a, BM, BN, bkc, 1, s)) return;
-  }
-  if (a.A2) {  // (unreachable: every planned tile has a kernel)
-    fprintf(stderr, "igemm_rows_dgrad_phases: no merged launch for a second source\n");
-    abort();
   }
   for (int i = 0; i < a.nphase; ++i) {  // one launch per phase
     const PhaseDesc& d = a.ph[i];
@@ -1089,196 +950,88 @@ void igemm_rows_dgrad_phases(IGemmArgs a, int vw, hipStream_t s, bool bkc) {
   }
 }
 
-template <int BM, int BN, int WM, int WN, int VWA, int VWB>
-static void launch_wgrad(const WGradArgs& a, int splits, hipStream_t s) {
-  dim3 grid(a.tiles_total, 1, splits);
-  const int o = occ_target();
-  if (o == 4)
-    hipLaunchKernelGGL((igemm_wgrad_kernel<BM, BN, WM, WN, VWA, VWB, 4>), grid, dim3(256), 0, s, a);
-  else if (o == 2)
-    hipLaunchKernelGGL((igemm_wgrad_kernel<BM, BN, WM, WN, VWA, VWB, 2>), grid, dim3(256), 0, s, a);
-  else
-    hipLaunchKernelGGL((igemm_wgrad_kernel<BM, BN, WM, WN, VWA, VWB, 3>), grid, dim3(256), 0, s, a);
-}
-
-template <int BM, int BN>
-static void wgrad_vw(const WGradArgs& a, int vwa, int vwb, int splits, hipStream_t s) {
-  if (vwb == 1) {
-    if (vwa == 8) launch_wgrad<BM, BN, 2, 2, 8, 1>(a, splits, s);
-    else if (vwa == 4) launch_wgrad<BM, BN, 2, 2, 4, 1>(a, splits, s);
-    else launch_wgrad<BM, BN, 2, 2, 1, 1>(a, splits, s);
-  } else {
-    if (vwa == 8) launch_wgrad<BM, BN, 2, 2, 8, 8>(a, splits, s);
-    else if (vwa == 4) launch_wgrad<BM, BN, 2, 2, 4, 8>(a, splits, s);
-    else launch_wgrad<BM, BN, 2, 2, 1, 8>(a, splits, s);
+// ----------------------------------------------------------------------- wgrad launches
+template <int BM, int BN, int WM, int WN>
+static void launch_wgrad_reg(const WGradLaunch& p, const WGradArgs& a, hipStream_t s) {
+  const dim3 grid(p.grid_x, 1, p.splits), block(p.block);
+  switch (p.VWA * 10 + p.VWB) {
+    case 81: hipLaunchKernelGGL((igemm_wgrad_kernel<BM, BN, WM, WN, 8, 1>), grid, block, 0, s, a); break;
+    case 41: hipLaunchKernelGGL((igemm_wgrad_kernel<BM, BN, WM, WN, 4, 1>), grid, block, 0, s, a); break;
+    case 11: hipLaunchKernelGGL((igemm_wgrad_kernel<BM, BN, WM, WN, 1, 1>), grid, block, 0, s, a); break;
+    case 88: hipLaunchKernelGGL((igemm_wgrad_kernel<BM, BN, WM, WN, 8, 8>), grid, block, 0, s, a); break;
+    case 48: hipLaunchKernelGGL((igemm_wgrad_kernel<BM, BN, WM, WN, 4, 8>), grid, block, 0, s, a); break;
+    case 18: hipLaunchKernelGGL((igemm_wgrad_kernel<BM, BN, WM, WN, 1, 8>), grid, block, 0, s, a); break;
+    default: no_kernel("igemm_wgrad_reg", p.BM, p.BN, p.WM, p.WN, p.VWA, p.VWB);
   }
 }
 
-// split over pixels: ~512 blocks (2 per CU), >= 16 K-steps per split, slab <= 64 MiB;
-// stem-shaped reductions (see wgrad_plan) target ~1024 blocks instead
-// big: the 8-wave 128x256 LDS-DMA tile (measured +20..40 % over the 4-wave tiles for
-// Kout >= 256 and for the stem's tiny-output / huge-pixel-count reduction)
-static bool wgrad_big(const WGradArgs& a, bool dma_ok) {
-  return dma_ok && (a.Kout >= 256 || ((int64_t)a.Kout * a.Ncols <= 32768 && a.Mpix >= (1 << 20)));
-}
-
-static bool wgrad_tile_ok(int bm, int bn, bool dma) {
-  const bool ok_reg = (bm == 64 || bm == 128) && bn == 128;
-  const bool ok_dma = ok_reg || (bn == 256 && (bm == 64 || bm == 128 || bm == 256));
-  return dma ? ok_dma : ok_reg;
-}
-
-static void wgrad_plan(WGradArgs& a, int& BM, int& BN, int& splits, bool dma, bool big,
-                       int tbm = 0, int tbn = 0) {
-  BM = (a.Kout <= 64) ? 64 : 128;
-  BN = 128;
-  // few 128-row tiles (e.g. a 1x1 downsample: Ncols = C_in): halve BM for parallelism
-  if (dma && BM == 128 && ((a.Kout + 127) / 128) * ((a.Ncols + 127) / 128) < 4) BM = 64;
-  if (big) BN = 256, BM = (a.Kout <= 64) ? 64 : 128;  // 64-row stems: no half-empty tile
-  const bool tuned = tbm && tbn && wgrad_tile_ok(tbm, tbn, dma);
-  if (tuned) { BM = tbm; BN = tbn; }
-  if (g_force_bm && g_force_bn && wgrad_tile_ok(g_force_bm, g_force_bn, dma)) {
-    BM = g_force_bm;
-    BN = g_force_bn;
+// register family: the rows of kWgradRegTiles
+static void igemm_wgrad_reg(const WGradLaunch& p, const WGradArgs& a, hipStream_t s) {
+  switch (p.BM * 1000 + p.BN) {
+    case 64128: launch_wgrad_reg<64, 128, 2, 2>(p, a, s); break;
+    case 128128: launch_wgrad_reg<128, 128, 2, 2>(p, a, s); break;
+    default: no_kernel("igemm_wgrad_reg", p.BM, p.BN, p.WM, p.WN, p.VWA, p.VWB);
   }
-  a.tiles_n = (a.Ncols + BN - 1) / BN;
-  const int tiles_m = (a.Kout + BM - 1) / BM;
-  a.tiles_total = tiles_m * a.tiles_n;
-  const int ktiles = (a.Mpix + BK - 1) / BK;
-  // stem-shaped reductions (64 output rows, 129..256 columns, >= 1M pixels): two 64x128
-  // column tiles x 512 splits instead of one 64x256 tile x 512 splits
-  // (profiles/stem_sweep_b512.txt, batch 512: 64x128/s512 439.4 us, 64x128/s1024 449.2 us,
-  // 64x256/s512 493.7 us). 512 splits keep the fp32 slab at 29 MB (1024: 58.7 MB).
-  const bool stem2 = big && BM == 64 && BN == 256 && !(g_force_bm && g_force_bn) && !tuned &&
-                     a.Ncols > 128 && a.Ncols <= 256;
-  if (stem2) {
-    BN = 128;
-    a.tiles_n = (a.Ncols + BN - 1) / BN;
-    a.tiles_total = tiles_m * a.tiles_n;
-  }
-  splits = std::max(1, ((stem2 ? 1024 : 512) + a.tiles_total - 1) / a.tiles_total);
-  splits = std::min(splits, std::max(1, ktiles / 16));
-  if (g_force_splits > 0) splits = std::min(g_force_splits, std::max(ktiles, 1));
-  const int64_t out = (int64_t)a.Kout * a.Ncols;
-  splits = (int)std::min<int64_t>(splits, std::max<int64_t>(1, (16ll << 20) / out));
-  finish_split_plan(ktiles, splits, a.ktiles_per_split);
 }
 
-int64_t igemm_wgrad_ws_floats(int Kout, int Ncols, int Mpix) {
-  int64_t best = conv3_halo_wgrad_ws_floats(Kout, Ncols);
-  if (Kout == 64 && Ncols == 224) best = std::max(best, stem_wgrad_ws_floats());
-  for (int dma = 0; dma < 3; ++dma) {  // register, DMA, DMA big tile
-    WGradArgs a{};
-    a.Kout = Kout; a.Ncols = Ncols; a.Mpix = Mpix;
-    int BM, BN, splits;
-    wgrad_plan(a, BM, BN, splits, dma >= 1, dma == 2);
-    if (splits > 1) best = std::max(best, (int64_t)splits * Kout * Ncols);
-  }
-  return best;
+// sums the z split partials of a.slab into a.dw (n = Kout * Ncols, n % 4 == 0)
+static void wgrad_reduce(const WGradArgs& a, int z, hipStream_t s) {
+  const int64_t n = (int64_t)a.Kout * a.Ncols;
+  hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(wgrad_reduce_blocks(n)), dim3(256), 0, s, a.slab, z, n,
+                     a.dw, a.overwrite);
 }
-
-static void wgrad_run_plan(WGradArgs a, int vwa, int vwb, hipStream_t s, int tbm, int tbn);
 
 void igemm_stem_pool_wgrad(WGradArgs a, StemPoolArgs q, hipStream_t s) {
-  const int z = stem_pool_wgrad(a, q, s);
-  const int64_t n = (int64_t)a.Kout * a.Ncols;
-  const int blocks = (int)std::max<int64_t>(1, (n / 4 + 63) / 64);
-  hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(blocks), dim3(256), 0, s, a.slab, z, n, a.dw,
-                     a.overwrite);
+  wgrad_reduce(a, stem_pool_wgrad(a, q, s), s);
 }
 
-static const int kWgradCands[][2] = {{64, 128}, {128, 128}, {64, 256}, {128, 256}, {256, 256}};
-
-// autotuned tile of a (non-halo) weight-gradient GEMM; candidates run on a scratch slab
-// and a scratch dw, and may not need more split slab than the caller allocated
-static void tuned_wgrad_tile(const WGradArgs& a, int vwa, int vwb, hipStream_t s, int& tbm,
-                             int& tbn) {
-  if (!g_tune || deterministic() || (g_force_bm && g_force_bn) || a.Mpix <= 0 ||
-      stream_capturing(s))
-    return;
-  char k[200];
-  snprintf(k, sizeof k, "wgrad K%d N%d P%d x%dx%dx%d o%dx%d f%dx%d s%d,%d p%d,%d", a.Kout, a.Ncols,
-           a.Mpix, a.H, a.W, a.C, a.P, a.Q, a.R, a.S, a.sh, a.sw, a.ph, a.pw);
-  const std::string key(k);
-  if (tuned_lookup(key, tbm, tbn)) return;
-  std::lock_guard<std::mutex> pass(g_tune_pass_mu);
-  if (tuned_lookup(key, tbm, tbn)) return;
-  const int64_t out = (int64_t)a.Kout * a.Ncols;
-  const int64_t cap = igemm_wgrad_ws_floats(a.Kout, a.Ncols, a.Mpix);
-  float best = 1e30f;
-  for (const auto& c : kWgradCands) {
-    if (c[0] > 64 && a.Kout <= 64) continue;  // half-empty tiles
-    if (c[1] == 256 && a.Ncols <= 128) continue;
-    WGradArgs b = a;
-    int BM, BN, sp;
-    const bool big = c[1] == 256;
-    wgrad_plan(b, BM, BN, sp, true, big, c[0], c[1]);
-    if (BM != c[0] || BN != c[1]) continue;
-    if (sp > 1 && (int64_t)sp * out > cap) continue;
-    char* scr = tune_scratch((size_t)(out + (sp > 1 ? sp * out : 0)) * 4 + 256);
-    if (!scr) return;
-    b = a;
-    b.dw = (float*)scr;
-    b.slab = a.slab ? (float*)scr + out : nullptr;
-    const float t = time_launches([&] { wgrad_run_plan(b, vwa, vwb, s, c[0], c[1]); }, s);
-    if (t < best) { best = t; tbm = c[0]; tbn = c[1]; }
-  }
-  if (tbm) tuned_store(key, tbm, tbn);
+// one planned weight-gradient GEMM and its split reduction
+static void launch_wgrad(const WGradLaunch& p, WGradArgs a, hipStream_t s) {
+  p.apply(a);
+  if (p.family == WGradFamily::Reg) igemm_wgrad_reg(p, a, s);
+  else igemm_wgrad_dma(p, a, s);
+  const int64_t n = (int64_t)a.Kout * a.Ncols;
+  if (p.reduce == WGradReduce::Vector)
+    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(p.reduce_blocks), dim3(256), 0, s, a.slab, p.splits,
+                       n, a.dw, a.overwrite);
+  else if (p.reduce == WGradReduce::Scalar)
+    hipLaunchKernelGGL(wgrad_reduce_scalar_kernel, dim3(p.reduce_blocks), dim3(256), 0, s, a.slab,
+                       p.splits, n, a.dw, a.overwrite);
 }
 
 void igemm_wgrad(WGradArgs a, int vwa, int vwb, hipStream_t s) {
-  const HaloWLaunch halo = igemm_engine() >= 1 ? conv3_halo_wgrad_plan(a) : HaloWLaunch{};
-  if (halo.kind != HaloWKind::None) {  // 3x3 / stride 1: halo-staged
-    const int z = conv3_halo_wgrad(a, halo, s);
-    const int64_t n = (int64_t)a.Kout * a.Ncols;  // Ncols = 9C, C % 32 == 0: float4 rows
-    const int blocks = (int)std::max<int64_t>(1, (n / 4 + 63) / 64);
-    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(blocks), dim3(256), 0, s, a.slab, z, n, a.dw,
-                       a.overwrite);
+  const GemmSwitches& sw = switches();
+  const HaloWLaunch halo = sw.engine >= 1 ? conv3_halo_wgrad_plan(a) : HaloWLaunch{};
+  if (halo.kind != HaloWKind::None) {  // 3x3 / stride 1: halo-staged (Ncols = 9C, C % 32 == 0)
+    wgrad_reduce(a, conv3_halo_wgrad(a, halo, s), s);
     return;
   }
-  if (igemm_engine() >= 1 && stem_wgrad_ok(a)) {  // pixel-pair 7x7 stem: halo-staged
-    const int z = stem_wgrad(a, s);
-    const int64_t n = (int64_t)a.Kout * a.Ncols;
-    const int blocks = (int)std::max<int64_t>(1, (n / 4 + 63) / 64);
-    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(blocks), dim3(256), 0, s, a.slab, z, n, a.dw,
-                       a.overwrite);
+  if (sw.engine >= 1 && stem_wgrad_ok(a)) {  // pixel-pair 7x7 stem: halo-staged
+    wgrad_reduce(a, stem_wgrad(a, s), s);
     return;
   }
-  const bool dma_ok = vwa == 8 && vwb == 8 && igemm_engine() >= 1;
-  int tbm = 0, tbn = 0;
-  if (dma_ok) tuned_wgrad_tile(a, vwa, vwb, s, tbm, tbn);
-  wgrad_run_plan(a, vwa, vwb, s, tbm, tbn);
-}
-
-// the GEMM + split reduction of igemm_wgrad for a given (tuned) tile
-static void wgrad_run_plan(WGradArgs a, int vwa, int vwb, hipStream_t s, int tbm, int tbn) {
-  int BM, BN, splits;
-  const bool dma_ok = vwa == 8 && vwb == 8 && igemm_engine() >= 1;
-  const bool big = (tbm && tbn) ? tbn == 256 : wgrad_big(a, dma_ok);
-  // engine 1: big 8-wave tile where it wins, else the incremental-pixel DMA kernel
-  // (tools/bench_kernels.py sweep: equal or faster than register staging on every
-  // ResNet-18 wgrad shape it covers), else register staging
-  const bool dma = big || (dma_ok && (igemm_engine() == 2 || igemm_wgrad_inc_ok(a)));
-  wgrad_plan(a, BM, BN, splits, dma, big, tbm, tbn);
-  if (dma && igemm_wgrad_dma(a, BM, BN, splits, s)) {
-    // LDS-DMA engine (igemm_dma.hip)
-  } else if (BM == 64) {
-    wgrad_vw<64, 128>(a, vwa, vwb, splits, s);
-  } else {
-    wgrad_vw<128, 128>(a, vwa, vwb, splits, s);
-  }
-  if (splits > 1) {
-    const int64_t n = (int64_t)a.Kout * a.Ncols;
-    if (n % 4 == 0) {  // float4 path: 16-B aligned split rows
-      const int blocks = (int)std::max<int64_t>(1, (n / 4 + 63) / 64);
-      hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(blocks), dim3(256), 0, s, a.slab, splits, n,
-                         a.dw, a.overwrite);
-    } else {
-      const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>((n + 255) / 256, 4096));
-      hipLaunchKernelGGL(wgrad_reduce_scalar_kernel, dim3(blocks), dim3(256), 0, s, a.slab,
-                         splits, n, a.dw, a.overwrite);
-    }
-  }
+  // autotuned tile of a (non-halo) weight-gradient GEMM; candidates run on a scratch slab
+  // and a scratch dw, and may not need more split slab than the caller allocated
+  TileSize tuned{0, 0};
+  if (vwa == 8 && vwb == 8 && sw.engine >= 1 && a.Mpix > 0)
+    tuned = tuned_tile<WGradRun>(
+        [&] { return wgrad_key(a); }, kWgradCands, s,
+        [&](TileSize c, WGradRun& r) {
+          if (!wgrad_cand_ok(c, a)) return Cand::Skip;
+          r.p = plan_wgrad(a, vwa, vwb, sw, c);
+          if (r.p.BM != c.bm || r.p.BN != c.bn) return Cand::Skip;
+          const int64_t out = (int64_t)a.Kout * a.Ncols;
+          if (r.p.splits > 1 && r.p.splits * out > igemm_wgrad_ws_floats(a.Kout, a.Ncols, a.Mpix))
+            return Cand::Skip;
+          char* scr = tune_scratch((size_t)(out + (r.p.splits > 1 ? r.p.splits * out : 0)) * 4 + 256);
+          if (!scr) return Cand::Stop;
+          r.a = a;
+          r.a.dw = (float*)scr;
+          r.a.slab = a.slab ? (float*)scr + out : nullptr;
+          return Cand::Ready;
+        },
+        [&](const WGradRun& r) { launch_wgrad(r.p, r.a, s); });
+  launch_wgrad(plan_wgrad(a, vwa, vwb, sw, tuned), a, s);
 }
 
 }  // namespace mpa

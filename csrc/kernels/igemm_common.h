@@ -4,14 +4,13 @@
 #pragma once
 #include "common.h"
 #include "api.h"
+#include "igemm_plan.h"
 
 namespace mpa {
 
 __device__ __forceinline__ u32x4 u32x4_make(uint32_t a, uint32_t b, uint32_t c, uint32_t d) {
   return u32x4{a, b, c, d};
 }
-
-constexpr int BK = 32;
 
 // ---------------------------------------------------------------------- LDS swizzles
 // K-contiguous image: [rows][32] bf16, 64-B rows, 4 x 16-B chunks per row.
@@ -446,12 +445,12 @@ __device__ __forceinline__ void wgrad_epilogue(const WGradArgs& p,
 }
 
 // ------------------------------------------------- LDS-DMA engine (igemm_dma.hip)
-// Launch the LDS-DMA variant of a planned rows / wgrad GEMM (16-B operand granularity
-// required).  Return false when no instantiation covers the tile shape.
-bool igemm_rows_dma(const IGemmArgs& a, int BM, int BN, bool bkc, int splits, hipStream_t s);
-bool igemm_rows_uni_src2_ok(const IGemmArgs& a, bool bkc);
-bool igemm_rows_kpad_ok(const IGemmArgs& a, bool bkc);
-bool igemm_wgrad_dma(const WGradArgs& a, int BM, int BN, int splits, hipStream_t s);
-bool igemm_wgrad_inc_ok(const WGradArgs& a);  // incremental-pixel wgrad kernel applies
+// Launch the LDS-DMA kernel a plan names (family Dma / DmaUni, Dma / DmaInc); the plan's
+// argument fields are already set in `a`.
+void igemm_rows_dma(const RowsLaunch& p, const IGemmArgs& a, hipStream_t s);
+void igemm_wgrad_dma(const WGradLaunch& p, const WGradArgs& a, hipStream_t s);
+// a dispatcher was handed a plan outside its family's tile table (x, y: the family's other
+// template arguments)
+[[noreturn]] void no_kernel(const char* what, int bm, int bn, int wm, int wn, int x, int y);
 
 }  // namespace mpa

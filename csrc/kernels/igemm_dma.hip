@@ -25,6 +25,7 @@
 // Requires 16-B granularity on both operands (the VW = 8 case of igemm.hip); the host
 // falls back to the register-staged engine otherwise.
 #include <algorithm>
+#include <cstdio>
 #include <cstdlib>
 #include <type_traits>
 #include "igemm_common.h"
@@ -595,13 +596,7 @@ void igemm_wgrad_dma_kernel(WGradArgs p) {
 //  channels past Kout and columns past R*S*C are clamped instead of masked (their
 //  results are never stored); pixels past Mpix read the zero page.
 // ======================================================================================
-struct WInc {   // per-launch scalar constants of the pixel walk
-  int dq_s, dp_s;          // sw * (32 % Q), sh * (32 / Q): per-step ow*sw / oh*sh advance
-  int qwrap, pwrap;        // Q * sw, P * sh: wrap thresholds of ow*sw and oh*sh
-  int step_off;            // input offset advance per step (no wrap)
-  int qwrap_off, pwrap_off;  // extra input offset on a column / image wrap
-};
-
+// (WInc, the per-launch scalar constants of the pixel walk: igemm_plan.h)
 template <int BM, int BN, int WM, int WN>
 __global__ __launch_bounds__(WM * WN * 64, dma_occ(3 * (BM + BN) * 64, WM * WN))
 void igemm_wgrad_dma_inc_kernel(WGradArgs p, WInc w) {
@@ -743,122 +738,67 @@ void igemm_wgrad_dma_inc_kernel(WGradArgs p, WInc w) {
 }
 
 // ======================================================================================
-//  host launchers (plans are made by igemm.hip)
+//  host launchers: one dispatcher per kernel family, from a plan's template arguments
+//  (igemm_plan.h) to the instantiation
 // ======================================================================================
-// uniform-tap fast path on/off (A/B and cross-checking; MPA_DMA_UNI=0 disables)
-static bool g_dma_uni = [] {
-  const char* e = getenv("MPA_DMA_UNI");
-  return !(e && e[0] == '0');
-}();
-void igemm_set_dma_uni(int on) { g_dma_uni = on != 0; }
-bool igemm_stap_ok() { return g_dma_uni && igemm_engine() >= 1; }
-// byte extents of the rows kernel's operands: the uniform-tap kernel addresses both with
-// 32-bit offsets
-static bool rows_uni_fits(const IGemmArgs& a, bool bkc) {
-  const PhaseDesc* d = a.nphase > 0 ? &a.ph[0] : nullptr;
-  const int64_t hw = d ? (int64_t)d->oH * d->oW : (int64_t)a.oH * a.oW;
-  const int64_t m = d ? d->M : a.M;
-  const int64_t nimg = hw > 0 ? (m + hw - 1) / hw : 0;
-  const int64_t abytes = nimg * a.aH * a.aW * a.aC * 2;
-  const int64_t bbytes = (bkc ? (int64_t)a.N : (int64_t)a.aC * a.RS) * a.ldb * 2;
-  const int64_t b2bytes = (int64_t)a.N * a.ldb2 * 2;
-  return abytes < (1ll << 31) && bbytes < (1ll << 31) && b2bytes < (1ll << 31);
-}
-
-// a second GEMM source is read only by the uniform-tap kernel's phase form with K-contiguous
-// B (launch_rows_dma_v picks that kernel under exactly these conditions)
-// kpad form available: the uniform-tap kernel with K-contiguous B takes the launch
-bool igemm_rows_kpad_ok(const IGemmArgs& a, bool bkc) {
-  return bkc && g_dma_uni && !a.stap && a.nphase == 0 && a.aC % BK != 0 && a.aC % 8 == 0 &&
-         rows_uni_fits(a, bkc);
-}
-
-bool igemm_rows_uni_src2_ok(const IGemmArgs& a, bool bkc) {
-  return bkc && a.nphase > 0 && a.aC % BK == 0 && !a.stap && g_dma_uni && rows_uni_fits(a, bkc);
-}
-
 template <int BM, int BN, int WM, int WN, bool BKC, bool SPLIT, bool PH>
-static void launch_rows_dma_v(const IGemmArgs& a0, dim3 grid, hipStream_t s) {
-  IGemmArgs a = a0;
-  igemm_set_fastdiv(a);
-  if ((a.aC % BK == 0 || a.stap || (a.kpad && BKC)) && g_dma_uni && rows_uni_fits(a, BKC))
-    hipLaunchKernelGGL((igemm_rows_dma_uni_kernel<BM, BN, WM, WN, BKC, SPLIT, PH>), grid,
-                       dim3(WM * WN * 64), 0, s, a);
+static void launch_rows_dma_v(const RowsLaunch& p, const IGemmArgs& a, hipStream_t s) {
+  const dim3 grid(p.grid_x, 1, p.splits), block(p.block);
+  if (p.family == RowsFamily::DmaUni)
+    hipLaunchKernelGGL((igemm_rows_dma_uni_kernel<BM, BN, WM, WN, BKC, SPLIT, PH>), grid, block, 0,
+                       s, a);
   else
-    hipLaunchKernelGGL((igemm_rows_dma_kernel<BM, BN, WM, WN, BKC, SPLIT, PH>), grid,
-                       dim3(WM * WN * 64), 0, s, a);
+    hipLaunchKernelGGL((igemm_rows_dma_kernel<BM, BN, WM, WN, BKC, SPLIT, PH>), grid, block, 0, s, a);
 }
 
 template <int BM, int BN, int WM, int WN, bool BKC>
-static void launch_rows_dma(const IGemmArgs& a, int splits, hipStream_t s) {
-  dim3 grid(a.tiles_total, 1, splits);
-  if (a.nphase > 0) {  // merged stride phases (dgrad): never split
-    launch_rows_dma_v<BM, BN, WM, WN, BKC, false, true>(a, grid, s);
+static void launch_rows_dma(const RowsLaunch& p, const IGemmArgs& a, hipStream_t s) {
+  if (p.PH) launch_rows_dma_v<BM, BN, WM, WN, BKC, false, true>(p, a, s);  // never split
+  else if (p.SPLIT) launch_rows_dma_v<BM, BN, WM, WN, BKC, true, false>(p, a, s);
+  else launch_rows_dma_v<BM, BN, WM, WN, BKC, false, false>(p, a, s);
+}
+
+// LDS-DMA rows families (generic and uniform-tap): the rows of kRowsDmaTiles
+template <bool BKC>
+static void rows_dma_tile(const RowsLaunch& p, const IGemmArgs& a, hipStream_t s) {
+  switch (p.BM * 1000 + p.BN) {
+    case 256256: launch_rows_dma<256, 256, 2, 4, BKC>(p, a, s); break;
+    case 256128: launch_rows_dma<256, 128, 2, 2, BKC>(p, a, s); break;
+    case 128128: launch_rows_dma<128, 128, 2, 2, BKC>(p, a, s); break;
+    case 256064: launch_rows_dma<256, 64, 4, 1, BKC>(p, a, s); break;
+    case 128064: launch_rows_dma<128, 64, 2, 2, BKC>(p, a, s); break;
+    case 128032: launch_rows_dma<128, 32, 4, 1, BKC>(p, a, s); break;
+    default: no_kernel("igemm_rows_dma", p.BM, p.BN, p.WM, p.WN, (int)p.family, p.BKC);
+  }
+}
+
+void igemm_rows_dma(const RowsLaunch& p, const IGemmArgs& a0, hipStream_t s) {
+  IGemmArgs a = a0;
+  igemm_set_fastdiv(a);
+  if (p.BKC) rows_dma_tile<true>(p, a, s);
+  else rows_dma_tile<false>(p, a, s);
+}
+
+// LDS-DMA wgrad families: the rows of kWgradIncTiles (incremental) and kWgradDmaTiles
+void igemm_wgrad_dma(const WGradLaunch& p, const WGradArgs& a, hipStream_t s) {
+  const dim3 grid(p.grid_x, 1, p.splits), block(p.block);
+  const int tile = p.BM * 1000 + p.BN;
+  if (p.family == WGradFamily::DmaInc) {
+    switch (tile) {
+      case 128128: hipLaunchKernelGGL((igemm_wgrad_dma_inc_kernel<128, 128, 2, 2>), grid, block, 0, s, a, p.inc); break;
+      case 64128: hipLaunchKernelGGL((igemm_wgrad_dma_inc_kernel<64, 128, 2, 2>), grid, block, 0, s, a, p.inc); break;
+      default: no_kernel("igemm_wgrad_dma", p.BM, p.BN, p.WM, p.WN, (int)p.family, 0);
+    }
     return;
   }
-  if (splits > 1) launch_rows_dma_v<BM, BN, WM, WN, BKC, true, false>(a, grid, s);
-  else launch_rows_dma_v<BM, BN, WM, WN, BKC, false, false>(a, grid, s);
-}
-
-template <bool BKC>
-static bool rows_dma_tile(const IGemmArgs& a, int BM, int BN, int splits, hipStream_t s) {
-  if (BM == 256 && BN == 256) launch_rows_dma<256, 256, 2, 4, BKC>(a, splits, s);
-  else if (BM == 256 && BN == 128) launch_rows_dma<256, 128, 2, 2, BKC>(a, splits, s);
-  else if (BM == 128 && BN == 128) launch_rows_dma<128, 128, 2, 2, BKC>(a, splits, s);
-  else if (BM == 256 && BN == 64) launch_rows_dma<256, 64, 4, 1, BKC>(a, splits, s);
-  else if (BM == 128 && BN == 64) launch_rows_dma<128, 64, 2, 2, BKC>(a, splits, s);
-  else if (BM == 128 && BN == 32) launch_rows_dma<128, 32, 4, 1, BKC>(a, splits, s);
-  else return false;
-  return true;
-}
-
-bool igemm_rows_dma(const IGemmArgs& a, int BM, int BN, bool bkc, int splits, hipStream_t s) {
-  return bkc ? rows_dma_tile<true>(a, BM, BN, splits, s) : rows_dma_tile<false>(a, BM, BN, splits, s);
-}
-
-// incremental pixel walk applicable: one wrap per step suffices, 32-bit offsets, and
-// 16-B granular operands on both sides (callers guarantee Kout % 8 == 0, C % 8 == 0)
-bool igemm_wgrad_inc_ok(const WGradArgs& a) {
-  return g_dma_uni && (BK / a.Q) + 1 <= a.P && a.Ncols >= 8 && a.Kout >= 8 &&
-         (int64_t)a.Mpix / (a.P * a.Q) * a.H * a.W * a.C < (1ll << 31);
-}
-
-template <int BM, int BN, int WM, int WN>
-static void launch_wgrad_inc(const WGradArgs& a, dim3 grid, hipStream_t s) {
-  WInc w;
-  w.dq_s = a.sw * (BK % a.Q);
-  w.dp_s = a.sh * (BK / a.Q);
-  w.qwrap = a.Q * a.sw;
-  w.pwrap = a.P * a.sh;
-  w.step_off = (w.dp_s * a.W + w.dq_s) * a.C;
-  w.qwrap_off = (a.sh * a.W - a.Q * a.sw) * a.C;
-  w.pwrap_off = (a.H - a.P * a.sh) * a.W * a.C;
-  hipLaunchKernelGGL((igemm_wgrad_dma_inc_kernel<BM, BN, WM, WN>), grid, dim3(WM * WN * 64), 0,
-                     s, a, w);
-}
-
-bool igemm_wgrad_dma(const WGradArgs& a, int BM, int BN, int splits, hipStream_t s) {
-  dim3 grid(a.tiles_total, 1, splits);
-  // incremental kernel for the 4-wave tiles; the 8-wave tiles keep the generic kernel
-  // (the extra per-lane pixel state costs them their second block per CU: 124 -> 166 VGPR)
-  if (igemm_wgrad_inc_ok(a) && BN == 128 && (BM == 128 || BM == 64)) {
-    if (BM == 128) launch_wgrad_inc<128, 128, 2, 2>(a, grid, s);
-    else launch_wgrad_inc<64, 128, 2, 2>(a, grid, s);
-    return true;
+  switch (tile) {
+    case 256256: hipLaunchKernelGGL((igemm_wgrad_dma_kernel<256, 256, 2, 4>), grid, block, 0, s, a); break;
+    case 128256: hipLaunchKernelGGL((igemm_wgrad_dma_kernel<128, 256, 2, 4>), grid, block, 0, s, a); break;
+    case 64256: hipLaunchKernelGGL((igemm_wgrad_dma_kernel<64, 256, 2, 4>), grid, block, 0, s, a); break;
+    case 128128: hipLaunchKernelGGL((igemm_wgrad_dma_kernel<128, 128, 2, 2>), grid, block, 0, s, a); break;
+    case 64128: hipLaunchKernelGGL((igemm_wgrad_dma_kernel<64, 128, 2, 2>), grid, block, 0, s, a); break;
+    default: no_kernel("igemm_wgrad_dma", p.BM, p.BN, p.WM, p.WN, (int)p.family, 0);
   }
-  if (BM == 256 && BN == 256)
-    hipLaunchKernelGGL((igemm_wgrad_dma_kernel<256, 256, 2, 4>), grid, dim3(512), 0, s, a);
-  else if (BM == 128 && BN == 256)
-    hipLaunchKernelGGL((igemm_wgrad_dma_kernel<128, 256, 2, 4>), grid, dim3(512), 0, s, a);
-  else if (BM == 64 && BN == 256)
-    hipLaunchKernelGGL((igemm_wgrad_dma_kernel<64, 256, 2, 4>), grid, dim3(512), 0, s, a);
-  else if (BM == 128 && BN == 128)
-    hipLaunchKernelGGL((igemm_wgrad_dma_kernel<128, 128, 2, 2>), grid, dim3(256), 0, s, a);
-  else if (BM == 64 && BN == 128)
-    hipLaunchKernelGGL((igemm_wgrad_dma_kernel<64, 128, 2, 2>), grid, dim3(256), 0, s, a);
-  else
-    return false;
-  return true;
 }
 
 }  // namespace mpa
