@@ -1186,19 +1186,37 @@ static MixLabels check_mix_labels(const Tensor& logits, const c10::optional<Tens
   return m;
 }
 
+// The logit adjustment's per-class term: float32, at least NC elements, contiguous, on the
+// logits' device (the kernels read bias[0:NC) with 16-byte loads); null when absent.
+static const float* check_logit_bias(const Tensor& logits, const c10::optional<Tensor>& bias) {
+  if (!(bias && bias->defined())) return nullptr;
+  TORCH_CHECK(bias->scalar_type() == torch::kFloat32, "cross-entropy: bias must be float32");
+  TORCH_CHECK(bias->device() == logits.device(), "cross-entropy: bias on another device");
+  TORCH_CHECK(bias->is_contiguous(), "cross-entropy: bias must be contiguous");
+  TORCH_CHECK(bias->numel() >= logits.size(1), "cross-entropy: bias must hold NC = ",
+              logits.size(1), " floats, got ", bias->numel());
+  const float* p = bias->data_ptr<float>();
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(p) % 16 == 0,
+              "cross-entropy: bias must be 16-byte aligned");
+  return p;
+}
+
 std::vector<Tensor> ce_fwd(Tensor logits, Tensor labels, double smoothing,
-                           c10::optional<Tensor> labels2, c10::optional<Tensor> lam) {
+                           c10::optional<Tensor> labels2, c10::optional<Tensor> lam,
+                           c10::optional<Tensor> bias) {
   const int ld = logits_ld(logits);
   const float eps = check_smoothing(smoothing);
   CHECK_CUDA(labels);
   TORCH_CHECK(labels.scalar_type() == torch::kInt64, "labels must be int64");
   const MixLabels mx = check_mix_labels(logits, labels2, lam);
+  const float* bs = check_logit_bias(logits, bias);
   const int B = logits.size(0), NC = logits.size(1);
   const c10::OptionalDeviceGuard g(device_of(logits));
   Tensor buf = torch::empty({1 + B}, logits.options().dtype(torch::kFloat32));
   Tensor lse = torch::empty({B}, logits.options().dtype(torch::kFloat32));
   mpa::ce_fwd(bp(logits), labels.contiguous().data_ptr<int64_t>(), B, NC, ld,
-              buf.data_ptr<float>(), lse.data_ptr<float>(), cur_stream(), eps, mx.labels2, mx.lam);
+              buf.data_ptr<float>(), lse.data_ptr<float>(), cur_stream(), eps, mx.labels2, mx.lam,
+              bs);
   return {buf.narrow(0, 0, 1), lse};
 }
 
@@ -1208,12 +1226,13 @@ std::vector<Tensor> ce_fwd(Tensor logits, Tensor labels, double smoothing,
 // returns the per-row log-sum-exp for the backward
 Tensor ce_fwd_weighted(Tensor logits, Tensor labels, Tensor out, Tensor acc, double weight,
                        bool accumulate, double smoothing, c10::optional<Tensor> labels2,
-                       c10::optional<Tensor> lam) {
+                       c10::optional<Tensor> lam, c10::optional<Tensor> bias) {
   const int ld = logits_ld(logits);
   const float eps = check_smoothing(smoothing);
   CHECK_CUDA(labels);
   TORCH_CHECK(labels.scalar_type() == torch::kInt64, "labels must be int64");
   const MixLabels mx = check_mix_labels(logits, labels2, lam);
+  const float* bs = check_logit_bias(logits, bias);
   CHECK_CUDA(out);
   CHECK_F32(out);
   TORCH_CHECK(out.numel() >= 1, "ce_fwd_weighted: out must hold one float");
@@ -1225,20 +1244,22 @@ Tensor ce_fwd_weighted(Tensor logits, Tensor labels, Tensor out, Tensor acc, dou
   mpa::ce_fwd_weighted(bp(logits), labels.contiguous().data_ptr<int64_t>(), B, NC, ld,
                        out.data_ptr<float>(), fopt_mut(acc), (float)weight, accumulate,
                        rows.data_ptr<float>(), lse.data_ptr<float>(), cur_stream(), eps,
-                       mx.labels2, mx.lam);
+                       mx.labels2, mx.lam, bs);
   return lse;
 }
 
 Tensor ce_bwd(Tensor logits, Tensor labels, Tensor lse, Tensor grad_out, double weight,
-              double smoothing, c10::optional<Tensor> labels2, c10::optional<Tensor> lam) {
+              double smoothing, c10::optional<Tensor> labels2, c10::optional<Tensor> lam,
+              c10::optional<Tensor> bias) {
   const int ld = logits_ld(logits);
   const float eps = check_smoothing(smoothing);
   const MixLabels mx = check_mix_labels(logits, labels2, lam);
+  const float* bs = check_logit_bias(logits, bias);
   const int B = logits.size(0), NC = logits.size(1);
   const c10::OptionalDeviceGuard g(device_of(logits));
   Tensor d = torch::empty({B, ld}, logits.options());
   mpa::ce_bwd(bp(logits), labels.contiguous().data_ptr<int64_t>(), fopt(lse), fopt(grad_out), B,
-              NC, ld, bpm(d), cur_stream(), (float)weight, eps, mx.labels2, mx.lam);
+              NC, ld, bpm(d), cur_stream(), (float)weight, eps, mx.labels2, mx.lam, bs);
   return ld == NC ? d : d.narrow(1, 0, NC);
 }
 
@@ -1248,6 +1269,29 @@ void argmax_correct(Tensor logits, Tensor labels, Tensor count) {
   const c10::OptionalDeviceGuard g(device_of(logits));
   mpa::argmax_correct(bp(logits), labels.contiguous().data_ptr<int64_t>(), logits.size(0),
                       logits.size(1), ld, count.data_ptr<int64_t>(), cur_stream());
+}
+
+// argmax_correct's count plus per-class counters: stats int64 [3][NC], contiguous (support,
+// predicted, true positives), both accumulated into
+void argmax_stats(Tensor logits, Tensor labels, Tensor count, Tensor stats) {
+  const int ld = logits_ld(logits);
+  const int64_t B = logits.size(0), NC = logits.size(1);
+  CHECK_CUDA(labels);
+  CHECK_CUDA(count);
+  CHECK_CUDA(stats);
+  TORCH_CHECK(labels.scalar_type() == torch::kInt64 && labels.numel() == B,
+              "argmax_stats: one int64 label per row");
+  TORCH_CHECK(count.scalar_type() == torch::kInt64 && count.numel() >= 1,
+              "count must be int64");
+  TORCH_CHECK(stats.scalar_type() == torch::kInt64 && stats.dim() == 2 && stats.size(0) == 3 &&
+                  stats.size(1) == NC && stats.is_contiguous(),
+              "argmax_stats: stats must be a contiguous int64 [3, NC] tensor");
+  TORCH_CHECK(labels.device() == logits.device() && count.device() == logits.device() &&
+                  stats.device() == logits.device(),
+              "argmax_stats: labels / count / stats on another device");
+  const c10::OptionalDeviceGuard g(device_of(logits));
+  mpa::argmax_stats(bp(logits), labels.contiguous().data_ptr<int64_t>(), (int)B, (int)NC, ld,
+                    count.data_ptr<int64_t>(), stats.data_ptr<int64_t>(), cur_stream());
 }
 
 // count += #{rows whose label is among the k largest logits}, ties to the lower index
@@ -2009,14 +2053,19 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("linear_wgrad", &linear_wgrad, py::arg("dy"), py::arg("x"), py::arg("dw"),
         py::arg("overwrite") = false);
   m.def("ce_fwd", &ce_fwd, py::arg("logits"), py::arg("labels"), py::arg("smoothing") = 0.0,
-        py::arg("labels2") = py::none(), py::arg("lam") = py::none());
+        py::arg("labels2") = py::none(), py::arg("lam") = py::none(),
+        py::arg("bias") = py::none());
   m.def("ce_bwd", &ce_bwd, py::arg("logits"), py::arg("labels"), py::arg("lse"),
         py::arg("grad_out"), py::arg("weight") = 1.0, py::arg("smoothing") = 0.0,
-        py::arg("labels2") = py::none(), py::arg("lam") = py::none());
+        py::arg("labels2") = py::none(), py::arg("lam") = py::none(),
+        py::arg("bias") = py::none());
   m.def("ce_fwd_weighted", &ce_fwd_weighted, py::arg("logits"), py::arg("labels"),
         py::arg("out"), py::arg("acc"), py::arg("weight"), py::arg("accumulate"),
-        py::arg("smoothing") = 0.0, py::arg("labels2") = py::none(), py::arg("lam") = py::none());
+        py::arg("smoothing") = 0.0, py::arg("labels2") = py::none(), py::arg("lam") = py::none(),
+        py::arg("bias") = py::none());
   m.def("argmax_correct", &argmax_correct);
+  m.def("argmax_stats", &argmax_stats, py::arg("logits"), py::arg("labels"), py::arg("count"),
+        py::arg("stats"));
   m.def("topk_correct", &topk_correct, py::arg("logits"), py::arg("labels"), py::arg("k"),
         py::arg("count"));
   m.def("adam_step", &adam_step);

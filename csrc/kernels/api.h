@@ -254,22 +254,26 @@ void split_channels(const bf16_raw* dy, const int* chans, int nseg, int pixels, 
 // zeros in columns NC..ld-1.  smoothing: torch's label_smoothing in [0, 1]; 0 runs the plain
 // kernels.  labels2 + lam (optional device arrays [B], both or neither): row r's target is
 // lam[r] * onehot(labels[r]) + (1 - lam[r]) * onehot(labels2[r]) before smoothing (Mixup /
-// CutMix); null runs the one-label kernels.
+// CutMix); null runs the one-label kernels.  bias (optional device array, fp32 [NC], 16-B
+// aligned): logit adjustment - the loss is CE of float(logits) + bias, the saved lse is that
+// sum's; only bias[0:NC) is read; null runs the unadjusted kernels.
 void ce_fwd_rows(const bf16_raw* logits, const int64_t* labels, int B, int NC, int ld, float* row_loss,
                  float* lse, hipStream_t s, float smoothing = 0.f,
-                 const int64_t* labels2 = nullptr, const float* lam = nullptr);
+                 const int64_t* labels2 = nullptr, const float* lam = nullptr,
+                 const float* bias = nullptr);
 // loss: [1 + B] floats (mean at [0], per-row terms after it; fixed-order sum)
 void ce_fwd(const bf16_raw* logits, const int64_t* labels, int B, int NC, int ld, float* loss,
             float* lse, hipStream_t s, float smoothing = 0.f, const int64_t* labels2 = nullptr,
-            const float* lam = nullptr);
+            const float* lam = nullptr, const float* bias = nullptr);
 void ce_bwd(const bf16_raw* logits, const int64_t* labels, const float* lse,
             const float* grad_out, int B, int NC, int ld, bf16_raw* dlogits, hipStream_t s,
             float weight = 1.f, float smoothing = 0.f, const int64_t* labels2 = nullptr,
-            const float* lam = nullptr);
+            const float* lam = nullptr, const float* bias = nullptr);
 void ce_fwd_weighted(const bf16_raw* logits, const int64_t* labels, int B, int NC, int ld,
                      float* out, float* acc, float weight, bool accumulate, float* rows,
                      float* lse, hipStream_t s, float smoothing = 0.f,
-                     const int64_t* labels2 = nullptr, const float* lam = nullptr);
+                     const int64_t* labels2 = nullptr, const float* lam = nullptr,
+                     const float* bias = nullptr);
 // fp32 t[0:n) = 0 (n % 4 == 0, 16-B aligned); step[0] += 1
 void zero_f32(float* t, int64_t n, hipStream_t s);
 void add_f32(float* dst, const float* src, int64_t n, hipStream_t s);  // dst += src
@@ -280,6 +284,11 @@ void add_bf16(bf16_raw* a, const bf16_raw* b, int64_t n, hipStream_t s);
 void step_inc(float* step, hipStream_t s);
 void argmax_correct(const bf16_raw* logits, const int64_t* labels, int B, int NC, int ld,
                     int64_t* count, hipStream_t s);
+// argmax_correct's count, and per-class counters stats int64 [3][NC]: for every row with a
+// label in [0, NC), stats[0][label] += 1 (support), stats[1][pred] += 1 (predicted; an all-NaN
+// row predicts nothing) and stats[2][label] += 1 when pred == label (true positives)
+void argmax_stats(const bf16_raw* logits, const int64_t* labels, int B, int NC, int ld,
+                  int64_t* count, int64_t* stats, hipStream_t s);
 // count += #{rows whose label is among the k largest logits}; ties go to the lower index
 // (k = 1 is argmax_correct); out-of-range labels and NaN label logits are not counted
 void topk_correct(const bf16_raw* logits, const int64_t* labels, int B, int NC, int ld, int k,

@@ -29,6 +29,17 @@
 // constexpr (MIX)" - the kernel arguments too (CeMix) - and null labels2 launches the
 // MIX = false instantiations: the one-label loss runs the code it ran before.
 //
+// ADJ (logit adjustment, Menon et al. 2021): the loss is CE of z = float(x) + bias with bias
+// fp32 [NC] (tau * log prior), added in registers - the bf16 logits in memory stay as they
+// are.  z takes x's place everywhere: the online LSE (the saved lse is lse(z)), the smoothed
+// sum, the picked logits and the backward's softmax.  bias is read with 16-B loads beside the
+// logit loads (two per 8 logits) and only in [0, NC): a vector that straddles NC reads its
+// valid columns one by one.  258 KB at NC = 64,500, so it stays in L2 and HBM still streams
+// only logits.  Everything it adds sits under "if constexpr (ADJ)" - the kernel argument too
+// (CeAdj, ahead of CeMix: empty, it sits in the padding in front of the mixed kernels'
+// pointers, so no existing argument moves) - and a null bias launches the ADJ = false
+// instantiations.
+//
 // Top-k accuracy (topk_correct): no selection or sort - a row is correct iff fewer than k
 // columns outrank its label's logit, ties going to the lower index (argmax_kernel's rule).
 #include "common.h"
@@ -77,14 +88,50 @@ struct CeMix<true> {
   const float* lam;        // [B]
 };
 
+// the ADJ instantiations' extra kernel argument (an empty argument otherwise)
+template <bool ADJ>
+struct CeAdj {};
+template <>
+struct CeAdj<true> {
+  const float* bias;  // [NC] fp32, 16-B aligned
+};
+
+// b[j] = bias[c0 + j] for the columns c0 + j < NC, 0 for the rest (never read); c0 % V == 0,
+// so a whole vector is V/4 aligned 16-B loads
+template <int V>
+__device__ __forceinline__ void load_bias(const float* __restrict__ bias, int c0, int NC,
+                                          float* b) {
+  if (c0 + V <= NC) {
+    if constexpr (V == 1) {
+      b[0] = bias[c0];
+    } else {
+#pragma unroll
+      for (int q = 0; q < V / 4; ++q) {
+        const float4 u = *(const float4*)(bias + c0 + 4 * q);
+        b[4 * q] = u.x; b[4 * q + 1] = u.y; b[4 * q + 2] = u.z; b[4 * q + 3] = u.w;
+      }
+    }
+  } else {
+#pragma unroll
+    for (int j = 0; j < V; ++j) b[j] = c0 + j < NC ? bias[c0 + j] : 0.f;
+  }
+}
+
+// the (adjusted) logit of column c, 0 <= c < NC
+template <bool ADJ>
+__device__ __forceinline__ float ce_pick(const bf16_t* x, int64_t c, const CeAdj<ADJ>& aj) {
+  if constexpr (ADJ) return bf2f(x[c]) + aj.bias[c];
+  else return bf2f(x[c]);
+}
+
 // Block-reduce the per-thread (m, s) - and, SMOOTH, the logit sum t - in a fixed order
 // (wave shuffle, then 4 LDS entries) and have thread 0 write the row's lse and loss term.
-template <bool SMOOTH, bool MIX>
+template <bool SMOOTH, bool MIX, bool ADJ>
 __device__ __forceinline__ void ce_row_finish(float m, float s, float t, const bf16_t* x, int row,
                                               const int64_t* __restrict__ labels, int B, int NC,
                                               float* __restrict__ row_loss,
                                               float* __restrict__ lse_out, float eps,
-                                              const CeMix<MIX>& mx) {
+                                              const CeMix<MIX>& mx, const CeAdj<ADJ>& aj) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) {
     const float m2 = __shfl_xor(m, o, 64), s2 = __shfl_xor(s, o, 64);
@@ -107,7 +154,8 @@ __device__ __forceinline__ void ce_row_finish(float m, float s, float t, const b
     if constexpr (MIX) {  // both labels valid (the callers' contract)
       const int64_t lab2 = mx.labels2[row];
       const bool ok = lab >= 0 && lab < NC && lab2 >= 0 && lab2 < NC;
-      const float picked = ce_mix2(mx.lam[row], bf2f(x[ok ? lab : 0]), bf2f(x[ok ? lab2 : 0]));
+      const float picked = ce_mix2(mx.lam[row], ce_pick<ADJ>(x, ok ? lab : 0, aj),
+                                   ce_pick<ADJ>(x, ok ? lab2 : 0, aj));
       if constexpr (SMOOTH) {
         const float T = (st[0] + st[1]) + (st[2] + st[3]);
         const float l = lse - (1.f - eps) * picked - (eps / (float)NC) * T;
@@ -117,22 +165,22 @@ __device__ __forceinline__ void ce_row_finish(float m, float s, float t, const b
       }
     } else if constexpr (SMOOTH) {
       const float T = (st[0] + st[1]) + (st[2] + st[3]);
-      const float l = lse - (1.f - eps) * bf2f(x[lab >= 0 && lab < NC ? lab : 0]) -
+      const float l = lse - (1.f - eps) * ce_pick<ADJ>(x, lab >= 0 && lab < NC ? lab : 0, aj) -
                       (eps / (float)NC) * T;
       row_loss[row] = (lab >= 0 && lab < NC) ? l / (float)B : 0.f;
     } else {
-      const float picked = (lab >= 0 && lab < NC) ? bf2f(x[lab]) : lse;
+      const float picked = (lab >= 0 && lab < NC) ? ce_pick<ADJ>(x, lab, aj) : lse;
       row_loss[row] = (lse - picked) / (float)B;
     }
   }
 }
 
-template <int V, bool SMOOTH = false, bool MIX = false>
+template <int V, bool SMOOTH = false, bool MIX = false, bool ADJ = false>
 __global__ __launch_bounds__(256) void ce_fwd_kernel(const bf16_t* __restrict__ logits,
                                                       const int64_t* __restrict__ labels, int B,
                                                       int NC, int ld, float* __restrict__ row_loss,
                                                       float* __restrict__ lse_out, float eps,
-                                                      CeMix<MIX> mx) {
+                                                      CeAdj<ADJ> aj, CeMix<MIX> mx) {
   const int row = blockIdx.x;
   const bf16_t* x = logits + (size_t)row * ld;
   float m = -INFINITY, s = 0.f, t = 0.f;
@@ -140,6 +188,12 @@ __global__ __launch_bounds__(256) void ce_fwd_kernel(const bf16_t* __restrict__ 
   for (int i = threadIdx.x; i < nv; i += 256) {
     float f[V];
     load_v<V>(x + (size_t)i * V, f);
+    if constexpr (ADJ) {
+      float b[V];
+      load_bias<V>(aj.bias, i * V, NC, b);
+#pragma unroll
+      for (int j = 0; j < V; ++j) f[j] += b[j];
+    }
     float lm = f[0];
 #pragma unroll
     for (int j = 1; j < V; ++j) lm = fmaxf(lm, f[j]);
@@ -154,30 +208,34 @@ __global__ __launch_bounds__(256) void ce_fwd_kernel(const bf16_t* __restrict__ 
       for (int j = 0; j < V; ++j) t += f[j];
     }
   }
-  ce_row_finish<SMOOTH, MIX>(m, s, t, x, row, labels, B, NC, row_loss, lse_out, eps, mx);
+  ce_row_finish<SMOOTH, MIX, ADJ>(m, s, t, x, row, labels, B, NC, row_loss, lse_out, eps, mx,
+                                  aj);
 }
 
 // Padded rows (ld % 8 == 0, 16-B aligned; the 64,500-class head has ld = 64,512): 16-B
 // loads over the whole padded row with columns >= NC masked to -inf, U loads issued before
 // any is consumed.  The unpadded kernel above walked 64,500 columns in 8-B loads, one load
 // per online-LSE step, and streamed ~2.2 TB/s (30 us per 66 MB of logits).
-template <int U, bool SMOOTH = false, bool MIX = false>
+template <int U, bool SMOOTH = false, bool MIX = false, bool ADJ = false>
 __global__ __launch_bounds__(256) void ce_fwd_padded_kernel(const bf16_t* __restrict__ logits,
                                                              const int64_t* __restrict__ labels,
                                                              int B, int NC, int ld,
                                                              float* __restrict__ row_loss,
                                                              float* __restrict__ lse_out,
-                                                             float eps, CeMix<MIX> mx) {
+                                                             float eps, CeAdj<ADJ> aj,
+                                                             CeMix<MIX> mx) {
   const int row = blockIdx.x;
   const bf16_t* x = logits + (size_t)row * ld;
   float m = -INFINITY, s = 0.f, t = 0.f;
   const int nv = ld / 8;
   for (int i0 = threadIdx.x; i0 < nv; i0 += 256 * U) {
     uint4 v[U];
+    float b[ADJ ? U : 1][8];  // ADJ: the bias of the same columns, in flight with the logits
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       const int i = i0 + u * 256;
       v[u] = i < nv ? *(const uint4*)(x + (size_t)i * 8) : make_uint4(0u, 0u, 0u, 0u);
+      if constexpr (ADJ) load_bias<8>(aj.bias, i * 8, NC, b[u]);  // (reads nothing at >= NC)
     }
 #pragma unroll
     for (int u = 0; u < U; ++u) {
@@ -185,6 +243,10 @@ __global__ __launch_bounds__(256) void ce_fwd_padded_kernel(const bf16_t* __rest
       if (c0 >= NC) continue;
       float f[8];
       unpack8(v[u], f);
+      if constexpr (ADJ) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) f[j] += b[u][j];
+      }
       float lm = -INFINITY;
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
@@ -200,19 +262,20 @@ __global__ __launch_bounds__(256) void ce_fwd_padded_kernel(const bf16_t* __rest
       s = acc;
     }
   }
-  ce_row_finish<SMOOTH, MIX>(m, s, t, x, row, labels, B, NC, row_loss, lse_out, eps, mx);
+  ce_row_finish<SMOOTH, MIX, ADJ>(m, s, t, x, row, labels, B, NC, row_loss, lse_out, eps, mx,
+                                  aj);
 }
 
 // SMOOTH: onw = 1 - eps is the label's weight, unif = eps / NC every class's share.
 // MIX: column c loses onw * (lam * [c == y] + (1 - lam) * [c == y2]).
-template <int V, bool SMOOTH = false, bool MIX = false>
+template <int V, bool SMOOTH = false, bool MIX = false, bool ADJ = false>
 __global__ __launch_bounds__(256) void ce_bwd_kernel(const bf16_t* __restrict__ logits,
                                                       const int64_t* __restrict__ labels,
                                                       const float* __restrict__ lse,
                                                       const float* __restrict__ grad_out, int B,
                                                       int NC, int ld, bf16_t* __restrict__ dlogits,
                                                       float weight, float onw, float unif,
-                                                      CeMix<MIX> mx) {
+                                                      CeAdj<ADJ> aj, CeMix<MIX> mx) {
   const float scale = grad_out[0] * weight / (float)B;
   const int nv = ld / V;  // whole padded row: columns >= NC get zero gradient
   const int64_t total = (int64_t)B * nv;
@@ -228,6 +291,12 @@ __global__ __launch_bounds__(256) void ce_bwd_kernel(const bf16_t* __restrict__ 
     float f[V];
     const size_t off = (size_t)row * ld + c0;
     load_v<V>(logits + off, f);
+    if constexpr (ADJ) {
+      float b[V];
+      load_bias<V>(aj.bias, c0, NC, b);
+#pragma unroll
+      for (int j = 0; j < V; ++j) f[j] += b[j];
+    }
 #pragma unroll
     for (int j = 0; j < V; ++j) {
       float p = __expf(f[j] - l);
@@ -283,6 +352,48 @@ __global__ __launch_bounds__(256) void argmax_kernel(const bf16_t* __restrict__ 
     for (int i = 1; i < 4; ++i)
       if (sv[i] > best || (sv[i] == best && si[i] < bi)) { best = sv[i]; bi = si[i]; }
     if ((int64_t)bi == labels[row]) atomicAdd(count, 1ull);
+  }
+}
+
+// argmax_kernel's row argmax (duplicated, so that kernel stays as it was) feeding per-class
+// counters as well: stats int64 [3][NC] = support, predicted, true positives.  count gets what
+// argmax_kernel adds.  A row whose label is outside [0, NC) touches no counter; an all-NaN
+// (or all -inf) row has no prediction (bi stays 0x7fffffff).  Integer atomics: exact under
+// contention and independent of their order.
+__global__ __launch_bounds__(256) void argmax_stats_kernel(const bf16_t* __restrict__ logits,
+                                                            const int64_t* __restrict__ labels,
+                                                            int NC, int ld,
+                                                            unsigned long long* __restrict__ count,
+                                                            unsigned long long* __restrict__ stats) {
+  const int row = blockIdx.x;
+  const bf16_t* x = logits + (size_t)row * ld;
+  float best = -INFINITY;
+  int bi = 0x7fffffff;
+  for (int i = threadIdx.x; i < NC; i += 256) {
+    const float v = bf2f(x[i]);
+    if (v > best) { best = v; bi = i; }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float v2 = __shfl_xor(best, o, 64);
+    const int i2 = __shfl_xor(bi, o, 64);
+    if (v2 > best || (v2 == best && i2 < bi)) { best = v2; bi = i2; }
+  }
+  __shared__ float sv[4];
+  __shared__ int si[4];
+  const int w = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 0) { sv[w] = best; si[w] = bi; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int i = 1; i < 4; ++i)
+      if (sv[i] > best || (sv[i] == best && si[i] < bi)) { best = sv[i]; bi = si[i]; }
+    const int64_t lab = labels[row];
+    if ((int64_t)bi == lab) atomicAdd(count, 1ull);
+    if (lab >= 0 && lab < NC) {
+      atomicAdd(stats + lab, 1ull);
+      if (bi < NC) atomicAdd(stats + (size_t)NC + bi, 1ull);
+      if ((int64_t)bi == lab) atomicAdd(stats + 2 * (size_t)NC + lab, 1ull);
+    }
   }
 }
 
@@ -369,9 +480,9 @@ __global__ __launch_bounds__(256) void ce_loss_sum_kernel(const float* __restric
 // loss: [1 + B] floats - the mean loss at [0], the per-row terms after it
 void ce_fwd(const bf16_raw* logits, const int64_t* labels, int B, int NC, int ld, float* loss,
             float* lse, hipStream_t s, float smoothing, const int64_t* labels2,
-            const float* lam) {
+            const float* lam, const float* bias) {
   float* rows = loss + 1;
-  ce_fwd_rows(logits, labels, B, NC, ld, rows, lse, s, smoothing, labels2, lam);
+  ce_fwd_rows(logits, labels, B, NC, ld, rows, lse, s, smoothing, labels2, lam, bias);
   hipLaunchKernelGGL(ce_loss_sum_kernel, dim3(1), dim3(256), 0, s, rows, B, loss,
                      0, 1.f, (float*)nullptr);
 }
@@ -381,111 +492,128 @@ void ce_fwd(const bf16_raw* logits, const int64_t* labels, int B, int NC, int ld
 void ce_fwd_weighted(const bf16_raw* logits, const int64_t* labels, int B, int NC, int ld,
                      float* out, float* acc, float weight, bool accumulate, float* rows,
                      float* lse, hipStream_t s, float smoothing, const int64_t* labels2,
-                     const float* lam) {
-  ce_fwd_rows(logits, labels, B, NC, ld, rows, lse, s, smoothing, labels2, lam);
+                     const float* lam, const float* bias) {
+  ce_fwd_rows(logits, labels, B, NC, ld, rows, lse, s, smoothing, labels2, lam, bias);
   hipLaunchKernelGGL(ce_loss_sum_kernel, dim3(1), dim3(256), 0, s, rows, B, out,
                      accumulate ? 1 : 0, weight, acc);
 }
 
-template <bool SMOOTH>
+// the forward's choice of kernel, for one flavour
+template <bool SMOOTH, bool MIX, bool ADJ>
 static void ce_fwd_rows_t(const bf16_raw* logits, const int64_t* labels, int B, int NC, int ld,
-                          float* loss, float* lse, hipStream_t s, float eps) {
+                          float* loss, float* lse, hipStream_t s, float eps, CeMix<MIX> mx,
+                          CeAdj<ADJ> aj) {
   if (ld % 8 == 0 && ld >= NC && reinterpret_cast<uintptr_t>(logits) % 16 == 0) {
-    hipLaunchKernelGGL((ce_fwd_padded_kernel<4, SMOOTH>), dim3(B), dim3(256), 0, s, logits,
-                       labels, B, NC, ld, loss, lse, eps, CeMix<false>{});
+    hipLaunchKernelGGL((ce_fwd_padded_kernel<4, SMOOTH, MIX, ADJ>), dim3(B), dim3(256), 0, s,
+                       logits, labels, B, NC, ld, loss, lse, eps, aj, mx);
     return;
   }
   const int g = NC % 8 == 0 && ld % 8 == 0 ? 8 : (NC % 4 == 0 && ld % 4 == 0 ? 4 : 1);
   if (g == 8)
-    hipLaunchKernelGGL((ce_fwd_kernel<8, SMOOTH>), dim3(B), dim3(256), 0, s, logits, labels, B,
-                       NC, ld, loss, lse, eps, CeMix<false>{});
+    hipLaunchKernelGGL((ce_fwd_kernel<8, SMOOTH, MIX, ADJ>), dim3(B), dim3(256), 0, s, logits,
+                       labels, B, NC, ld, loss, lse, eps, aj, mx);
   else if (g == 4)
-    hipLaunchKernelGGL((ce_fwd_kernel<4, SMOOTH>), dim3(B), dim3(256), 0, s, logits, labels, B,
-                       NC, ld, loss, lse, eps, CeMix<false>{});
+    hipLaunchKernelGGL((ce_fwd_kernel<4, SMOOTH, MIX, ADJ>), dim3(B), dim3(256), 0, s, logits,
+                       labels, B, NC, ld, loss, lse, eps, aj, mx);
   else
-    hipLaunchKernelGGL((ce_fwd_kernel<1, SMOOTH>), dim3(B), dim3(256), 0, s, logits, labels, B,
-                       NC, ld, loss, lse, eps, CeMix<false>{});
+    hipLaunchKernelGGL((ce_fwd_kernel<1, SMOOTH, MIX, ADJ>), dim3(B), dim3(256), 0, s, logits,
+                       labels, B, NC, ld, loss, lse, eps, aj, mx);
 }
 
-// the same choice of kernel with two labels per row
-template <bool SMOOTH>
-static void ce_fwd_rows_mix_t(const bf16_raw* logits, const int64_t* labels, int B, int NC,
-                              int ld, float* loss, float* lse, hipStream_t s, float eps,
-                              const int64_t* labels2, const float* lam) {
-  if (ld % 8 == 0 && ld >= NC && reinterpret_cast<uintptr_t>(logits) % 16 == 0) {
-    hipLaunchKernelGGL((ce_fwd_padded_kernel<4, SMOOTH, true>), dim3(B), dim3(256), 0, s, logits,
-                       labels, B, NC, ld, loss, lse, eps, CeMix<true>{labels2, lam});
-    return;
-  }
-  const int g = NC % 8 == 0 && ld % 8 == 0 ? 8 : (NC % 4 == 0 && ld % 4 == 0 ? 4 : 1);
-  if (g == 8)
-    hipLaunchKernelGGL((ce_fwd_kernel<8, SMOOTH, true>), dim3(B), dim3(256), 0, s, logits, labels,
-                       B, NC, ld, loss, lse, eps, CeMix<true>{labels2, lam});
-  else if (g == 4)
-    hipLaunchKernelGGL((ce_fwd_kernel<4, SMOOTH, true>), dim3(B), dim3(256), 0, s, logits, labels,
-                       B, NC, ld, loss, lse, eps, CeMix<true>{labels2, lam});
+template <bool SMOOTH, bool MIX>
+static void ce_fwd_rows_a(const bf16_raw* logits, const int64_t* labels, int B, int NC, int ld,
+                          float* loss, float* lse, hipStream_t s, float eps, CeMix<MIX> mx,
+                          const float* bias) {
+  if (bias)
+    ce_fwd_rows_t<SMOOTH, MIX, true>(logits, labels, B, NC, ld, loss, lse, s, eps, mx,
+                                     CeAdj<true>{bias});
   else
-    hipLaunchKernelGGL((ce_fwd_kernel<1, SMOOTH, true>), dim3(B), dim3(256), 0, s, logits, labels,
-                       B, NC, ld, loss, lse, eps, CeMix<true>{labels2, lam});
+    ce_fwd_rows_t<SMOOTH, MIX, false>(logits, labels, B, NC, ld, loss, lse, s, eps, mx,
+                                      CeAdj<false>{});
 }
 
 // smoothing == 0 launches the SMOOTH = false instantiations, null labels2 the one-label
-// ones (the plain loss, unchanged)
+// ones, null bias the unadjusted ones (the plain loss, unchanged)
 void ce_fwd_rows(const bf16_raw* logits, const int64_t* labels, int B, int NC, int ld, float* loss,
                  float* lse, hipStream_t s, float smoothing, const int64_t* labels2,
-                 const float* lam) {
+                 const float* lam, const float* bias) {
   if (labels2) {
+    const CeMix<true> mx{labels2, lam};
     if (smoothing != 0.f)
-      ce_fwd_rows_mix_t<true>(logits, labels, B, NC, ld, loss, lse, s, smoothing, labels2, lam);
+      ce_fwd_rows_a<true, true>(logits, labels, B, NC, ld, loss, lse, s, smoothing, mx, bias);
     else
-      ce_fwd_rows_mix_t<false>(logits, labels, B, NC, ld, loss, lse, s, 0.f, labels2, lam);
+      ce_fwd_rows_a<false, true>(logits, labels, B, NC, ld, loss, lse, s, 0.f, mx, bias);
     return;
   }
-  if (smoothing != 0.f) ce_fwd_rows_t<true>(logits, labels, B, NC, ld, loss, lse, s, smoothing);
-  else ce_fwd_rows_t<false>(logits, labels, B, NC, ld, loss, lse, s, 0.f);
+  if (smoothing != 0.f)
+    ce_fwd_rows_a<true, false>(logits, labels, B, NC, ld, loss, lse, s, smoothing,
+                               CeMix<false>{}, bias);
+  else
+    ce_fwd_rows_a<false, false>(logits, labels, B, NC, ld, loss, lse, s, 0.f, CeMix<false>{},
+                                bias);
 }
 
-template <bool SMOOTH>
+template <bool SMOOTH, bool MIX, bool ADJ>
 static void ce_bwd_t(const bf16_raw* logits, const int64_t* labels, const float* lse,
                      const float* grad_out, int B, int NC, int ld, bf16_raw* dlogits,
-                     hipStream_t s, float weight, float eps, const int64_t* labels2,
-                     const float* lam) {
+                     hipStream_t s, float weight, float eps, CeMix<MIX> mx, CeAdj<ADJ> aj) {
   const int V = (ld % 8 == 0) ? 8 : (ld % 4 == 0 ? 4 : 1);
   const int64_t total = (int64_t)B * (ld / V);
   const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>((total + 255) / 256, 8192));
   const float onw = 1.f - eps, unif = eps / (float)NC;
 #define CE_BWD(VV)                                                                               \
-  do {                                                                                           \
-    if (labels2)                                                                                 \
-      hipLaunchKernelGGL((ce_bwd_kernel<VV, SMOOTH, true>), dim3(blocks), dim3(256), 0, s,       \
-                         logits, labels, lse, grad_out, B, NC, ld, dlogits, weight, onw, unif,   \
-                         CeMix<true>{labels2, lam});                                             \
-    else                                                                                         \
-      hipLaunchKernelGGL((ce_bwd_kernel<VV, SMOOTH>), dim3(blocks), dim3(256), 0, s, logits,     \
-                         labels, lse, grad_out, B, NC, ld, dlogits, weight, onw, unif,           \
-                         CeMix<false>{});                                                        \
-  } while (0)
+  hipLaunchKernelGGL((ce_bwd_kernel<VV, SMOOTH, MIX, ADJ>), dim3(blocks), dim3(256), 0, s,       \
+                     logits, labels, lse, grad_out, B, NC, ld, dlogits, weight, onw, unif, aj, mx)
   if (V == 8) CE_BWD(8);
   else if (V == 4) CE_BWD(4);
   else CE_BWD(1);
 #undef CE_BWD
 }
 
+template <bool SMOOTH, bool MIX>
+static void ce_bwd_a(const bf16_raw* logits, const int64_t* labels, const float* lse,
+                     const float* grad_out, int B, int NC, int ld, bf16_raw* dlogits,
+                     hipStream_t s, float weight, float eps, CeMix<MIX> mx, const float* bias) {
+  if (bias)
+    ce_bwd_t<SMOOTH, MIX, true>(logits, labels, lse, grad_out, B, NC, ld, dlogits, s, weight,
+                                eps, mx, CeAdj<true>{bias});
+  else
+    ce_bwd_t<SMOOTH, MIX, false>(logits, labels, lse, grad_out, B, NC, ld, dlogits, s, weight,
+                                 eps, mx, CeAdj<false>{});
+}
+
 void ce_bwd(const bf16_raw* logits, const int64_t* labels, const float* lse,
             const float* grad_out, int B, int NC, int ld, bf16_raw* dlogits, hipStream_t s,
-            float weight, float smoothing, const int64_t* labels2, const float* lam) {
+            float weight, float smoothing, const int64_t* labels2, const float* lam,
+            const float* bias) {
+  if (labels2) {
+    const CeMix<true> mx{labels2, lam};
+    if (smoothing != 0.f)
+      ce_bwd_a<true, true>(logits, labels, lse, grad_out, B, NC, ld, dlogits, s, weight,
+                           smoothing, mx, bias);
+    else
+      ce_bwd_a<false, true>(logits, labels, lse, grad_out, B, NC, ld, dlogits, s, weight, 0.f,
+                            mx, bias);
+    return;
+  }
   if (smoothing != 0.f)
-    ce_bwd_t<true>(logits, labels, lse, grad_out, B, NC, ld, dlogits, s, weight, smoothing,
-                   labels2, lam);
+    ce_bwd_a<true, false>(logits, labels, lse, grad_out, B, NC, ld, dlogits, s, weight,
+                          smoothing, CeMix<false>{}, bias);
   else
-    ce_bwd_t<false>(logits, labels, lse, grad_out, B, NC, ld, dlogits, s, weight, 0.f, labels2,
-                    lam);
+    ce_bwd_a<false, false>(logits, labels, lse, grad_out, B, NC, ld, dlogits, s, weight, 0.f,
+                           CeMix<false>{}, bias);
 }
 
 void argmax_correct(const bf16_raw* logits, const int64_t* labels, int B, int NC, int ld,
                     int64_t* count, hipStream_t s) {
   hipLaunchKernelGGL(argmax_kernel, dim3(B), dim3(256), 0, s, logits, labels, NC, ld,
                      (unsigned long long*)count);
+}
+
+void argmax_stats(const bf16_raw* logits, const int64_t* labels, int B, int NC, int ld,
+                  int64_t* count, int64_t* stats, hipStream_t s) {
+  hipLaunchKernelGGL(argmax_stats_kernel, dim3(B), dim3(256), 0, s, logits, labels, NC, ld,
+                     (unsigned long long*)count, (unsigned long long*)stats);
 }
 
 // count += #{rows whose label is among the k largest logits} (ties to the lower index)

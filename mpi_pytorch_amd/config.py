@@ -78,6 +78,9 @@ class Config:
     augment: str = "none"                  # none | flip | rrc (random-resized crop + flip)
     aug_scale_min: float = 0.08            # rrc: smallest crop, as a fraction of the image area
     label_smoothing: float = 0.0           # training-loss label smoothing in [0, 1] (0 = off)
+    # long-tail head (data/longtail.py, metrics.py; both off by default)
+    logit_adjust_tau: float = 0.0          # training loss on logits + tau * log(class prior); 0 = off
+    eval_macro: bool = False               # also report macro-F1 and balanced accuracy
     # sample mixing of the training loader (data/augment.py::sample_mix): images blended in
     # the preprocess launch, labels in the fused cross-entropy; off when both alphas are 0
     mixup_alpha: float = 0.0               # Mixup: lam ~ Beta(alpha, alpha)
@@ -140,6 +143,8 @@ class Config:
             raise ValueError("aug_scale_min must be in (0, 1]")
         if not 0.0 <= self.label_smoothing <= 1.0:
             raise ValueError("label_smoothing must be in [0, 1]")
+        if not self.logit_adjust_tau >= 0.0:
+            raise ValueError("logit_adjust_tau must be >= 0 (0 = off)")
         if not (self.mixup_alpha >= 0.0 and self.cutmix_alpha >= 0.0):
             raise ValueError("mixup_alpha and cutmix_alpha must be >= 0 (0 = off)")
         if not (0.0 <= self.mix_prob <= 1.0 and 0.0 <= self.mix_switch_prob <= 1.0):

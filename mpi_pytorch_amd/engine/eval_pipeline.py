@@ -45,6 +45,8 @@ from ..data.manifest import SyntheticImages, FolderImages, images_available, syn
 from ..models import initialize_model, input_spec
 from ..ops import functional as Fn
 from ..parallel import init_world, reduce_scalar, shard_dataframe, broadcast_object, ParamArena
+from ..parallel.comm import mpi_all_reduce
+from ..metrics import macro_scores
 from ..utils.logging import init_logger
 
 
@@ -73,7 +75,7 @@ def load_predictor(cfg: Config, device, ckpt_path: Optional[str] = None):
 class StreamPipeline:
     def __init__(self, model, device, out_hw, lanes: int = 1, depth: int = 4,
                  assign: str = "random", seed: int = 0, mode: int = 1, cpad=None, pad=None,
-                 topk: int = 0):
+                 topk: int = 0, macro: bool = False):
         self.model = model
         if cpad is None:  # the model stem's input layout (models.input_spec)
             spec = input_spec(model, out_hw)
@@ -99,18 +101,35 @@ class StreamPipeline:
         self.topk = int(topk) if topk and topk > 1 else 0
         self.topk_counts = [torch.zeros(1, dtype=torch.int64, device=self.device)
                             for _ in range(self.lanes)] if self.topk else []
+        # macro: per-lane per-class counters int64 [3, NC] (support, predicted, true
+        # positives), filled by the argmax pass that fills ``counts`` (made at the first batch,
+        # when the head's width is known)
+        self.macro = bool(macro)
+        self.stats = [None] * self.lanes if self.macro else []
         self.seen = [0] * self.lanes
         self._pinned = {}
         self._last_slot = None
 
     def _count(self, out, labels, lane: int) -> None:
-        Fn.count_correct(out, labels, self.counts[lane])
+        if self.macro:
+            if self.stats[lane] is None:
+                self.stats[lane] = torch.zeros(3, out.shape[1], dtype=torch.int64,
+                                               device=self.device)
+            Fn.count_class_stats(out, labels, self.counts[lane], self.stats[lane])
+        else:
+            Fn.count_correct(out, labels, self.counts[lane])
         if self.topk:
             Fn.count_topk(out, labels, self.topk, self.topk_counts[lane])
 
     def topk_correct(self) -> List[int]:
         """Per-lane top-k correct counts (empty unless ``topk > 1``); call after a run."""
         return [int(c.item()) for c in self.topk_counts]
+
+    def class_stats(self) -> Optional[torch.Tensor]:
+        """The lanes' per-class counters summed, int64 [3, NC] on the device (None unless
+        ``macro`` and a batch was seen); call after a run."""
+        got = [s for s in self.stats if s is not None]
+        return torch.stack(got).sum(0) if got else None
 
     def _lane_for(self, i: int) -> int:
         if self.assign == "roundrobin":
@@ -249,6 +268,16 @@ class StreamPipeline:
         return [int(c.item()) for c in self.counts]
 
 
+def global_class_stats(pipe: StreamPipeline, num_classes: int) -> torch.Tensor:
+    """``pipe``'s per-class counters summed over its lanes, then over the ranks (int64
+    [3, num_classes] on every rank): integer counts, so the order does not matter.  A
+    collective: every rank calls it."""
+    stats = pipe.class_stats()
+    if stats is None:  # (a rank whose shard is empty)
+        stats = torch.zeros(3, num_classes, dtype=torch.int64, device=pipe.device)
+    return mpi_all_reduce(stats)
+
+
 def pad_batch(imgs):
     """A list of uint8 HWC images of different sizes -> one zero-padded [B, Hmax, Wmax, 3]
     batch and the per-image extents [B, 2] (each image at the top-left of its slot)."""
@@ -382,7 +411,7 @@ def run_pipeline(cfg: Config, ckpt_path: Optional[str] = None, max_images: int =
         source = SyntheticImages((side, side) if side > 0 else tuple(out_hw))
     model = load_predictor(cfg, world.device, ckpt_path)
     pipe = StreamPipeline(model, world.device, out_hw, cfg.eval_lanes, assign=cfg.eval_assign,
-                          seed=cfg.seed + world.rank, topk=cfg.eval_topk)
+                          seed=cfg.seed + world.rank, topk=cfg.eval_topk, macro=cfg.eval_macro)
     t0 = time.perf_counter()
     if world.device.type == "cuda":
         pitch = None
@@ -413,10 +442,14 @@ def run_pipeline(cfg: Config, ckpt_path: Optional[str] = None, max_images: int =
     total_k = None
     if pipe.topk:
         total_k = reduce_scalar(sum(pipe.topk_correct()) / max(dataset_size, 1), root=0)
+    macro = macro_scores(global_class_stats(pipe, cfg.NUM_CLASSES)) if pipe.macro else None
     if world.rank == 0:
         log.info("Accuracy is {}".format(total))
         if pipe.topk:
             log.info("Top-{} accuracy is {}".format(pipe.topk, total_k))
+        if macro is not None:
+            log.info("Macro-F1 is {}".format(macro["macro_f1"]))
+            log.info("Balanced accuracy is {}".format(macro["balanced_acc"]))
         # the source extent is part of the number: a synthetic source at the model's input
         # size skips the downscale real ~1000x677 herbarium JPEGs need (cfg.eval_src)
         src = "real images" if isinstance(source, FolderImages) else \

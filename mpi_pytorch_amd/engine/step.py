@@ -54,13 +54,17 @@ class MixedLabels(NamedTuple):
     lam: torch.Tensor
 
 
-def loss_fn(out, labels, acc=None, label_smoothing=0.0):
+def loss_fn(out, labels, acc=None, label_smoothing=0.0, logit_bias=None):
     """CE; Inception's train-mode (logits, aux) uses loss + 0.4 * aux_loss (the documented
     fix of the reference's broken Inception path), one fused native op.
     ``labels``: a label tensor, or :class:`MixedLabels` (every head mixes the same way);
     ``acc``: device scalar the loss is also added to (the trainer's running sum);
-    ``label_smoothing``: torch's ``label_smoothing``, applied to every head."""
+    ``label_smoothing``: torch's ``label_smoothing``, applied to every head;
+    ``logit_bias``: the logit adjustment's per-class term (fp32 [>= NC] on the device), added
+    to every head's logits inside the loss kernels."""
     kw = dict(acc=acc, label_smoothing=label_smoothing)
+    if logit_bias is not None:
+        kw["logit_bias"] = logit_bias
     if isinstance(labels, MixedLabels):
         labels, kw["labels2"], kw["lam"] = labels
     if isinstance(out, (tuple, InceptionOutputs)):
@@ -197,7 +201,7 @@ class StepTimer:
 
 class TrainStep:
     def __init__(self, model: nn.Module, optimizer, world: World, label_smoothing: float = 0.0,
-                 ema: Optional[ModelEMA] = None):
+                 ema: Optional[ModelEMA] = None, logit_bias: Optional[torch.Tensor] = None):
         self.model = model
         self.opt = optimizer
         # weight EMA (ema.py): updated right after the optimizer, inside the "opt" phase -
@@ -205,6 +209,11 @@ class TrainStep:
         self.ema = ema
         self.world = world
         self.label_smoothing = float(label_smoothing)  # a host constant: graph-capture safe
+        # logit adjustment: a constant device tensor (fixed address, never rewritten), so a
+        # captured graph needs nothing new; None = off, the loss launches what it always did
+        self.logit_bias = None
+        if logit_bias is not None:
+            self.logit_bias = logit_bias.to(model._mpa_arena.device, torch.float32).contiguous()
         self.arena: ParamArena = model._mpa_arena
         self.bucketer: GradBucketer = model._mpa_bucketer
         self.opt.grad_scale = 1.0 / world.world_size
@@ -251,7 +260,8 @@ class TrainStep:
         Fn.branch_streams(single)
         try:
             out = self.model(x)
-            loss = loss_fn(out, y, acc=self.loss_sum, label_smoothing=self.label_smoothing)
+            loss = loss_fn(out, y, acc=self.loss_sum, label_smoothing=self.label_smoothing,
+                           logit_bias=self.logit_bias)
         except BaseException:
             Fn.branch_streams(False)
             raise
@@ -416,13 +426,16 @@ def build_training(name: str, num_classes: int, device, world: World, lr: float,
                    comm_dtype: str = "fp32", comm_ctas: Optional[int] = None,
                    schedule: Optional[dict] = None, clip_grad_norm: float = 0.0,
                    label_smoothing: float = 0.0, trust_coef: float = 0.001,
-                   wd_exclude_1d: bool = True, ema_decay: float = 0.0, ema_warmup: bool = True):
+                   wd_exclude_1d: bool = True, ema_decay: float = 0.0, ema_warmup: bool = True,
+                   logit_bias: Optional[torch.Tensor] = None):
     """``schedule``: keyword arguments of ``optim.set_schedule`` (None: constant LR);
     ``clip_grad_norm`` > 0: global-norm gradient clipping (``optim.set_clip``);
     ``label_smoothing``: the training loss's label smoothing in [0, 1];
     ``trust_coef`` / ``wd_exclude_1d``: the layer-wise optimizers' settings (adamw | lamb |
     lars only); ``ema_decay`` > 0: a weight EMA (``ema.ModelEMA``) as ``step.ema``, started
-    from the synced weights (``ema_warmup``: ``min(decay, (1 + t) / (10 + t))``)."""
+    from the synced weights (``ema_warmup``: ``min(decay, (1 + t) / (10 + t))``);
+    ``logit_bias``: fp32 [>= num_classes], the training loss's logit adjustment
+    (``data.longtail.logit_bias``; None = off)."""
     model, input_size = build_model(name, num_classes, feature_extract, device, world,
                                     bucket_mb=bucket_mb, overlap=overlap, comm_dtype=comm_dtype,
                                     comm_ctas=comm_ctas)
@@ -437,4 +450,6 @@ def build_training(name: str, num_classes: int, device, world: World, lr: float,
     if not 0.0 <= ema_decay < 1.0:
         raise ValueError("ema_decay must be in [0, 1) (0 = off)")
     ema = ModelEMA(model, opt, ema_decay, ema_warmup) if ema_decay > 0.0 else None
-    return model, opt, TrainStep(model, opt, world, label_smoothing, ema), input_size
+    if logit_bias is not None and (logit_bias.dim() != 1 or logit_bias.numel() < num_classes):
+        raise ValueError("logit_bias must be a vector of at least num_classes elements")
+    return model, opt, TrainStep(model, opt, world, label_smoothing, ema, logit_bias), input_size

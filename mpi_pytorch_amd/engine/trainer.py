@@ -37,6 +37,8 @@ from ..data.manifest import (read_manifests, synthetic_manifest, SyntheticImages
                              images_available)
 from ..data.loader import IMAGENET_MEAN, IMAGENET_STD
 from ..data.augment import sample_boxes, sample_ids, sample_mix, label_weights
+from ..data.longtail import logit_bias as longtail_bias
+from ..metrics import macro_scores
 from ..ops import functional as Fn
 from ..parallel import (init_world, get_world, barrier, scatter_object, broadcast_object,
                         all_gather_object,
@@ -191,6 +193,17 @@ def _image_source(cfg: Config, names: Sequence[str], src_hw):
     return SyntheticImages(src_hw)
 
 
+def shared_logit_bias(cfg: Config, labels, rank: int) -> Optional[torch.Tensor]:
+    """The training loss's logit adjustment ``tau * log(prior)`` (fp32 [NUM_CLASSES], host), or
+    None at ``logit_adjust_tau`` 0.  ``labels``: the ``category_id`` column of the whole
+    (unsharded) manifest, which only rank 0 holds: computed there and broadcast, so every
+    rank adds the same vector bitwise.  A collective when on: every rank calls it."""
+    if not cfg.logit_adjust_tau > 0.0:
+        return None
+    return broadcast_object(longtail_bias(labels, cfg.NUM_CLASSES, cfg.logit_adjust_tau)
+                            if rank == 0 else None)
+
+
 def run_training(cfg: Config) -> dict:
     world = init_world(cfg.device, cfg.timeout_s, comm_timing=cfg.step_timers)
     rank, size = world.rank, world.world_size
@@ -214,6 +227,8 @@ def run_training(cfg: Config) -> dict:
     my = scatter_object(shards, root=0)
     log.info("_Files Received: {}".format(len(my)))
     n_total = int(broadcast_object(len(train_sample) if rank == 0 else None))
+    logit_bias = shared_logit_bias(
+        cfg, train_sample["category_id"].values if rank == 0 else None, rank)
     steps_per_epoch = equal_step_count(array_split_sizes(n_total, size), cfg.BATCH_SIZE)
     if cfg.max_steps:
         steps_per_epoch = min(steps_per_epoch, cfg.max_steps)
@@ -257,7 +272,8 @@ def run_training(cfg: Config) -> dict:
         cfg.grad_comm_dtype, None if cfg.grad_comm_ctas < 0 else cfg.grad_comm_ctas,
         schedule=schedule, clip_grad_norm=cfg.clip_grad_norm,
         label_smoothing=cfg.label_smoothing, trust_coef=cfg.trust_coef,
-        wd_exclude_1d=cfg.wd_exclude_1d, ema_decay=cfg.ema_decay, ema_warmup=cfg.ema_warmup)
+        wd_exclude_1d=cfg.wd_exclude_1d, ema_decay=cfg.ema_decay, ema_warmup=cfg.ema_warmup,
+        logit_bias=logit_bias)
     log.info("_Model Created: {}".format(cfg.MODEL_NAME))
     spec = input_spec(model, out_hw)
     for ld in (train_loader, val_loader):
@@ -283,6 +299,9 @@ def run_training(cfg: Config) -> dict:
     log.info("_Model loaded to CPU")
     log.debug("_Compute device: %s", dev)  # (no such line in the reference)
     log.info("_Entering training Loop")
+    if logit_bias is not None:  # (no such line in the reference)
+        log.info("_Logit adjustment: tau {} | bias in [{}, {}]".format(
+            cfg.logit_adjust_tau, float(logit_bias.min()), float(logit_bias.max())))
     if cfg.mix_spec is not None:  # (no such line in the reference)
         log.info("_Sample mixing: mixup_alpha {} | cutmix_alpha {} | prob {} | switch_prob {}"
                  .format(cfg.mixup_alpha, cfg.cutmix_alpha, cfg.mix_prob, cfg.mix_switch_prob))
@@ -358,20 +377,29 @@ def run_training(cfg: Config) -> dict:
             if val_loader is not None:
                 log.info("_Evaluating model")
                 topk = cfg.eval_topk if cfg.eval_topk > 1 else 0
-                acc, acc_k = _evaluate(model, val_loader, topk)
+                acc, acc_k, macro = _evaluate(model, val_loader, topk, cfg.eval_macro)
                 rec["acc"] = acc
                 log.info("_Epoch: {} | Acc: {}".format(epoch, acc))
                 if topk:
                     rec["acc_top{}".format(topk)] = acc_k
                     log.info("_Epoch: {} | Top-{} Acc: {}".format(epoch, topk, acc_k))
+                if macro is not None:
+                    rec["macro_f1"], rec["balanced_acc"] = macro["macro_f1"], macro["balanced_acc"]
+                    log.info("_Epoch: {} | Macro-F1: {} | Balanced Acc: {}".format(
+                        epoch, macro["macro_f1"], macro["balanced_acc"]))
                 if step.ema is not None:  # a second pass over the averaged model
                     with step.ema.swapped_in():
-                        acc, acc_k = _evaluate(model, val_loader, topk)
+                        acc, acc_k, macro = _evaluate(model, val_loader, topk, cfg.eval_macro)
                     rec["acc_ema"] = acc
                     log.info("_Epoch: {} | EMA Acc: {}".format(epoch, acc))
                     if topk:
                         rec["acc_ema_top{}".format(topk)] = acc_k
                         log.info("_Epoch: {} | EMA Top-{} Acc: {}".format(epoch, topk, acc_k))
+                    if macro is not None:
+                        rec["macro_f1_ema"] = macro["macro_f1"]
+                        rec["balanced_acc_ema"] = macro["balanced_acc"]
+                        log.info("_Epoch: {} | EMA Macro-F1: {} | EMA Balanced Acc: {}".format(
+                            epoch, macro["macro_f1"], macro["balanced_acc"]))
         metrics.write(**rec)
         history.append(rec)
         if size > 1:
@@ -382,23 +410,31 @@ def run_training(cfg: Config) -> dict:
 
 
 @torch.no_grad()
-def _evaluate(model, loader: ManifestBatches, topk: int = 0):
-    """(top-1 accuracy, top-k accuracy or None) from one pass: each batch's forward feeds
-    both counters."""
+def _evaluate(model, loader: ManifestBatches, topk: int = 0, macro: bool = False):
+    """(top-1 accuracy, top-k accuracy or None, ``metrics.macro_scores`` or None) from one
+    pass: each batch's forward feeds every counter.  ``macro``: the argmax pass also fills
+    per-class counters (one read of the logits for top-1 either way)."""
     model.eval()
     dev = loader.device
     count = torch.zeros(1, dtype=torch.int64, device=dev)
     count_k = torch.zeros(1, dtype=torch.int64, device=dev) if topk > 1 else None
+    stats = None
     n = 0
     for x, y in loader.epoch(0):
         out = model(x)
-        Fn.count_correct(out, y, count)
+        if macro:
+            if stats is None:
+                stats = torch.zeros(3, out.shape[1], dtype=torch.int64, device=dev)
+            Fn.count_class_stats(out, y, count, stats)
+        else:
+            Fn.count_correct(out, y, count)
         if count_k is not None:
             Fn.count_topk(out, y, topk, count_k)
         n += x.shape[0]
     model.train()
     return (float(count.item()) / max(n, 1),
-            float(count_k.item()) / max(n, 1) if count_k is not None else None)
+            float(count_k.item()) / max(n, 1) if count_k is not None else None,
+            macro_scores(stats) if stats is not None else None)
 
 
 def evaluate(model, loader: ManifestBatches) -> float:

@@ -1302,16 +1302,18 @@ class _CrossEntropy(torch.autograd.Function):
     by its weight - no elementwise ATen ops for Inception's ``loss + 0.4 * aux_loss``."""
 
     @staticmethod
-    def forward(ctx, labels, weights, acc, smoothing, mix, *logits):
+    def forward(ctx, labels, weights, acc, smoothing, mix, bias, *logits):
         k = K(logits[0])
         out = torch.empty(1, device=logits[0].device, dtype=torch.float32)
+        adj = {} if bias is None else {"bias": bias}  # (off: the call it always was)
         lses = [k.ce_fwd_weighted(lg, labels, out, _or_empty(acc, lg), float(w), i > 0, smoothing,
-                                  *mix)
+                                  *mix, **adj)
                 for i, (lg, w) in enumerate(zip(logits, weights))]
         ctx.weights = weights
         ctx.smoothing = smoothing  # one eps for every head, as a torch criterion applies it
         ctx.mixed = bool(mix)      # ... and one (labels2, lam): the aux head mixes the same way
-        ctx.save_for_backward(labels, *mix, *logits, *lses)
+        ctx.adjusted = bias is not None  # ... and one bias: the aux head has the same classes
+        ctx.save_for_backward(labels, *mix, *([] if bias is None else [bias]), *logits, *lses)
         return out.reshape(())
 
     @staticmethod
@@ -1320,15 +1322,19 @@ class _CrossEntropy(torch.autograd.Function):
         labels, rest, n = saved[0], saved[1:], len(ctx.weights)
         mix = rest[:2] if ctx.mixed else ()
         rest = rest[len(mix):]
+        adj = {}
+        if ctx.adjusted:
+            adj, rest = {"bias": rest[0]}, rest[1:]
         logits, lses = rest[:n], rest[n:]
         go = go.reshape(1).float().contiguous()
-        gs = [K(lg).ce_bwd(lg, labels, lse, go, float(w), ctx.smoothing, *mix)
+        gs = [K(lg).ce_bwd(lg, labels, lse, go, float(w), ctx.smoothing, *mix, **adj)
               for lg, lse, w in zip(logits, lses, ctx.weights)]
-        return (None, None, None, None, None) + tuple(gs)
+        return (None, None, None, None, None, None) + tuple(gs)
 
 
 def cross_entropy(logits, labels, weight: float = 1.0, acc: Optional[torch.Tensor] = None,
-                  heads=None, label_smoothing: float = 0.0, labels2=None, lam=None):
+                  heads=None, label_smoothing: float = 0.0, labels2=None, lam=None,
+                  logit_bias=None):
     """Mean softmax cross-entropy (``nn.CrossEntropyLoss()`` at main.py:134,150).
 
     ``heads``: extra (logits, weight) terms summed into the same loss (Inception aux);
@@ -1336,7 +1342,10 @@ def cross_entropy(logits, labels, weight: float = 1.0, acc: Optional[torch.Tenso
     ``label_smoothing``: torch's ``label_smoothing`` in [0, 1], applied to every head;
     ``labels2`` / ``lam`` (int64 / float32 [B] on the logits' device; Mixup / CutMix): row
     r's target is lam[r] * onehot(labels[r]) + (1 - lam[r]) * onehot(labels2[r]), for every
-    head; lam is read on the device, so a captured graph replays with new weights."""
+    head; lam is read on the device, so a captured graph replays with new weights;
+    ``logit_bias`` (float32 [>= NC] on the logits' device; logit adjustment, Menon et al.
+    2021): the loss is that of ``float(logits) + logit_bias[:NC]``, for every head - the
+    add happens in fp32 inside the loss kernels, the logits themselves are not changed."""
     eps = float(label_smoothing)
     if not 0.0 <= eps <= 1.0:
         raise ValueError("label_smoothing must be in [0, 1], got %r" % (label_smoothing,))
@@ -1346,17 +1355,25 @@ def cross_entropy(logits, labels, weight: float = 1.0, acc: Optional[torch.Tenso
     lg = [logits] + [h[0] for h in (heads or [])]
     ws = (float(weight),) + tuple(float(h[1]) for h in (heads or []))
     if torch.is_grad_enabled() and any(t.requires_grad for t in lg):
-        return _CrossEntropy.apply(labels, ws, acc, eps, mix, *lg)
+        return _CrossEntropy.apply(labels, ws, acc, eps, mix, logit_bias, *lg)
     k = K(logits)
     out = torch.empty(1, device=logits.device, dtype=torch.float32)
+    adj = {} if logit_bias is None else {"bias": logit_bias}
     for i, (t, w) in enumerate(zip(lg, ws)):
-        k.ce_fwd_weighted(t, labels, out, _or_empty(acc, t), w, i > 0, eps, *mix)
+        k.ce_fwd_weighted(t, labels, out, _or_empty(acc, t), w, i > 0, eps, *mix, **adj)
     return out.reshape(())
 
 
 def count_correct(logits, labels, count: torch.Tensor) -> None:
     """count += #(argmax(logits) == labels)  (main.py:182-183)."""
     K(logits).argmax_correct(logits, labels, count)
+
+
+def count_class_stats(logits, labels, count: torch.Tensor, stats: torch.Tensor) -> None:
+    """``count_correct`` and, in the same pass over the logits, per-class counters:
+    ``stats`` int64 [3, NC] += (support, predicted, true positives) of the rows whose label
+    is in [0, NC) (``metrics.macro_scores`` turns them into macro-F1 / balanced accuracy)."""
+    K(logits).argmax_stats(logits, labels, count, stats)
 
 
 def count_topk(logits, labels, k: int, count: torch.Tensor) -> None:

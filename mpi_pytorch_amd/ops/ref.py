@@ -544,11 +544,18 @@ def linear_wgrad(dy, x, dw, overwrite=False):
 
 
 # --------------------------------------------------------------------------- loss / acc
-def ce_fwd(logits, labels, smoothing=0.0, labels2=None, lam=None):
+def _adjusted(logits, bias):
+    """fp32 logits, plus the logit adjustment's per-class term ``bias[:NC]`` when given."""
+    lf = _f(logits)
+    return lf if bias is None else lf + _f(bias)[:lf.shape[1]]
+
+
+def ce_fwd(logits, labels, smoothing=0.0, labels2=None, lam=None, bias=None):
     """``smoothing``: torch's ``label_smoothing`` - the target is (1 - eps) * onehot + eps / NC.
     ``labels2`` / ``lam`` [B] (Mixup / CutMix): onehot is lam * onehot(labels) + (1 - lam) *
-    onehot(labels2)."""
-    lf = _f(logits)
+    onehot(labels2).  ``bias`` fp32 [>= NC] (logit adjustment): the loss and the returned lse
+    are those of ``float(logits) + bias[:NC]``."""
+    lf = _adjusted(logits, bias)
     lse = torch.logsumexp(lf, dim=1)
     picked = lf.gather(1, labels.view(-1, 1).long()).squeeze(1)
     if labels2 is not None:
@@ -561,9 +568,10 @@ def ce_fwd(logits, labels, smoothing=0.0, labels2=None, lam=None):
     return rows.mean().reshape(1), lse
 
 
-def ce_bwd(logits, labels, lse, grad_out, weight=1.0, smoothing=0.0, labels2=None, lam=None):
+def ce_bwd(logits, labels, lse, grad_out, weight=1.0, smoothing=0.0, labels2=None, lam=None,
+           bias=None):
     B, NC = logits.shape
-    p = torch.exp(_f(logits) - lse[:, None])
+    p = torch.exp(_adjusted(logits, bias) - lse[:, None])
     if smoothing:
         p -= smoothing / NC
     rows = torch.arange(B, device=logits.device)
@@ -579,8 +587,8 @@ def ce_bwd(logits, labels, lse, grad_out, weight=1.0, smoothing=0.0, labels2=Non
 
 
 def ce_fwd_weighted(logits, labels, out, acc, weight, accumulate, smoothing=0.0, labels2=None,
-                    lam=None):
-    loss, lse = ce_fwd(logits, labels, smoothing, labels2, lam)
+                    lam=None, bias=None):
+    loss, lse = ce_fwd(logits, labels, smoothing, labels2, lam, bias)
     v = loss.reshape(1) * weight
     if accumulate:
         out[:1] += v
@@ -602,6 +610,29 @@ def step_inc(step):
 def argmax_correct(logits, labels, count):
     pred = _f(logits).argmax(1)
     count.add_((pred == labels.long()).sum().to(count.dtype))
+
+
+def argmax_stats(logits, labels, count, stats):
+    """``argmax_correct``'s count, and per-class counters ``stats`` int64 [3, NC] (support,
+    predicted, true positives).  The prediction is the first index of the row's largest
+    non-NaN logit; a row without one (all NaN or -inf) predicts nothing.  For a row with a
+    label in [0, NC): stats[0][label] += 1, stats[1][pred] += 1 (when there is a prediction),
+    stats[2][label] += 1 (when pred == label).  Other rows touch no counter; count gains the
+    rows with pred == label."""
+    lf = _f(logits)
+    NC = lf.shape[1]
+    lab = labels.long()
+    v = torch.where(torch.isnan(lf), torch.full_like(lf, float("-inf")), lf)
+    best = v.max(1, keepdim=True).values
+    idx = torch.arange(NC, device=lf.device).view(1, -1)
+    first = torch.where(v == best, idx, NC).min(1).values
+    pred = torch.where(best.squeeze(1) > float("-inf"), first, torch.full_like(first, 0x7fffffff))
+    count.add_((pred == lab).sum().to(count.dtype))
+    valid = (lab >= 0) & (lab < NC)
+    one = lambda sel: torch.bincount(sel, minlength=NC).to(stats.dtype)
+    stats[0] += one(lab[valid])
+    stats[1] += one(pred[valid & (pred < NC)])
+    stats[2] += one(lab[valid & (pred == lab)])
 
 
 def topk_correct(logits, labels, k, count):

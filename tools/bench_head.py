@@ -3,9 +3,12 @@ linear fwd / dgrad / wgrad at [batch, 512] x [64,512, 512], the fused CE fwd / b
 wgrad tile sweep (forced BM x BN, splits).  The loss head is also timed smoothed
 (label smoothing 0.1) against plain, and topk_correct (k = 1, 5) against argmax_correct: each
 variant warmed, three alternating repetitions, so the plain kernel's own spread stands next
-to every difference.
+to every difference.  ``ce pair`` is a forward followed by its backward.  ``--adjust`` adds
+the long-tail head: the logit-adjusted CE (a Zipf-like log-prior bias) forward, backward and
+pair, and argmax_stats against argmax_correct.
 
-    python tools/bench_head.py [batch] [iters] [loss]     (loss: stop after the loss head)
+    python tools/bench_head.py [batch] [iters] [loss] [--adjust]
+                                                         (loss: stop after the loss head)
 """
 import os
 import sys
@@ -15,6 +18,8 @@ import torch
 
 from mpi_pytorch_amd.ops import _ext
 
+ADJUST = "--adjust" in sys.argv
+sys.argv = [a for a in sys.argv if a != "--adjust"]
 B = int(sys.argv[1]) if len(sys.argv) > 1 else 512
 IT = int(sys.argv[2]) if len(sys.argv) > 2 else 20
 C = _ext.ext()
@@ -67,7 +72,25 @@ groups = [
     [("argmax_correct", lambda: C.argmax_correct(logits, labels, cnt)),
      ("topk k=1", lambda: C.topk_correct(logits, labels, 1, cnt)),
      ("topk k=5", lambda: C.topk_correct(logits, labels, 5, cnt))],
+    [("ce pair", lambda: pair())],
 ]
+
+
+def pair(*tail):
+    _, l_ = C.ce_fwd(logits, labels, *tail)
+    C.ce_bwd(logits, labels, l_, go, 1.0, *tail)
+
+
+if ADJUST:
+    rank = torch.randperm(64500, device=dev).double() + 1.0
+    bias = torch.log((1.0 / rank) / (1.0 / rank).sum()).float()
+    _, lse_a = C.ce_fwd(logits, labels, 0.0, None, None, bias)
+    stats = torch.zeros(3, 64500, dtype=torch.int64, device=dev)
+    groups[0].append(("ce_fwd adj", lambda: C.ce_fwd(logits, labels, 0.0, None, None, bias)))
+    groups[1].append(("ce_bwd adj",
+                      lambda: C.ce_bwd(logits, labels, lse_a, go, 1.0, 0.0, None, None, bias)))
+    groups[2].append(("argmax_stats", lambda: C.argmax_stats(logits, labels, cnt, stats)))
+    groups[3].append(("ce pair adj", lambda: pair(0.0, None, None, bias)))
 print("loss head, 3 alternating repetitions: us (min .. max)")
 for group in groups:
     times = {name: [] for name, _ in group}
