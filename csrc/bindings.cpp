@@ -1310,6 +1310,27 @@ void topk_correct(Tensor logits, Tensor labels, int64_t k, Tensor count) {
                     count.data_ptr<int64_t>(), cur_stream());
 }
 
+// idx int32 [B, k] / prob float32 [B, k], contiguous (a row window of a larger buffer is), both
+// written: the k best classes of every row and their softmax probabilities
+void topk_predict(Tensor logits, int64_t k, Tensor idx, Tensor prob) {
+  const int ld = logits_ld(logits);
+  const int64_t B = logits.size(0), NC = logits.size(1);
+  TORCH_CHECK(k >= 1 && k <= 16, "topk_predict: k must be in [1, 16], got ", k);
+  CHECK_CUDA(idx);
+  CHECK_CUDA(prob);
+  TORCH_CHECK(idx.device() == logits.device() && prob.device() == logits.device(),
+              "topk_predict: idx / prob on another device");
+  TORCH_CHECK(idx.scalar_type() == at::kInt && idx.dim() == 2 && idx.size(0) == B &&
+                  idx.size(1) == k && idx.is_contiguous(),
+              "topk_predict: idx must be a contiguous int32 [B, k] tensor");
+  TORCH_CHECK(prob.scalar_type() == torch::kFloat32 && prob.dim() == 2 && prob.size(0) == B &&
+                  prob.size(1) == k && prob.is_contiguous(),
+              "topk_predict: prob must be a contiguous float32 [B, k] tensor");
+  const c10::OptionalDeviceGuard g(device_of(logits));
+  mpa::topk_predict(bp(logits), (int)B, (int)NC, ld, (int)k, idx.data_ptr<int>(),
+                    prob.data_ptr<float>(), cur_stream());
+}
+
 // ----------------------------------------------------------------------------- optim
 void adam_step(Tensor p, Tensor g, Tensor m, Tensor v, Tensor shadow, Tensor step, double lr,
                double b1, double b2, double eps, double wd, double gs) {
@@ -2068,6 +2089,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("stats"));
   m.def("topk_correct", &topk_correct, py::arg("logits"), py::arg("labels"), py::arg("k"),
         py::arg("count"));
+  m.def("topk_predict", &topk_predict, py::arg("logits"), py::arg("k"), py::arg("idx"),
+        py::arg("prob"));
   m.def("adam_step", &adam_step);
   m.def("sgd_step", &sgd_step);
   m.def("grad_sqnorm", &grad_sqnorm,

@@ -293,6 +293,12 @@ void argmax_stats(const bf16_raw* logits, const int64_t* labels, int B, int NC, 
 // (k = 1 is argmax_correct); out-of-range labels and NaN label logits are not counted
 void topk_correct(const bf16_raw* logits, const int64_t* labels, int B, int NC, int ld, int k,
                   int64_t* count, hipStream_t s);
+// idx int32 [B][k] / prob fp32 [B][k], 1 <= k <= 16: the row's k best classes in topk_correct's
+// order (x[c] > x[d], or equal and c < d) and their softmax probabilities; NaN and -inf logits
+// are no candidates, and slots past the last candidate get idx = -1, prob = 0.  No atomics: a
+// row's outputs depend on that row alone
+void topk_predict(const bf16_raw* logits, int B, int NC, int ld, int k, int* idx, float* prob,
+                  hipStream_t s);
 
 // optim.hip (flat fp32 arenas)
 void adam_step(float* p, const float* g, float* m, float* v, bf16_raw* shadow,

@@ -454,6 +454,148 @@ __global__ __launch_bounds__(256) void topk_kernel(const bf16_t* __restrict__ lo
   if (threadIdx.x == 0 && sn[0] + sn[1] + sn[2] + sn[3] < k) atomicAdd(count, 1ull);
 }
 
+// ---- topk_predict: which classes won, and their softmax probabilities, in one pass.
+//
+// Candidates are the columns c < NC whose logit is neither NaN nor -inf; c outranks d when
+// x[c] > x[d], or x[c] == x[d] and c < d (argmax_kernel's rule).  idx[row][j] is the candidate
+// that exactly j candidates outrank, prob[row][j] = exp(x[idx] - lse) with lse the fp32
+// log-sum-exp of the row's NC columns (ce_fwd's quantity); slots past the last candidate get
+// idx = -1, prob = 0.
+//
+// Each lane walks its columns in rising order with an online (max, sum) pair and a sorted list
+// of its K best (value, index) pairs: arrays indexed only by unrolled constants, so they live in
+// registers.  A new value enters the list only when it is greater than the list's last entry,
+// and inside the list it passes only smaller entries: equal values keep their column order.
+// The row's k best are among the lanes' lists, so the block then runs k rounds: the lanes' list
+// heads are reduced (wave shuffles, then four LDS entries; each round has its own entries, so
+// one barrier per round is enough), thread 0 writes the winner and the lane that held it pops
+// its head.  No atomics and a fixed reduction order: a row's outputs depend on that row alone.
+
+constexpr int TOP_NONE = 0x7fffffff;  // the index of an empty list slot (argmax_kernel's "none")
+
+// (v, c) outranks (v2, c2)
+__device__ __forceinline__ bool top_outranks(float v, int c, float v2, int c2) {
+  return v > v2 || (v == v2 && c < c2);
+}
+
+// insert (v, c) into the descending list; the caller has checked v > lv[K - 1]
+template <int K>
+__device__ __forceinline__ void top_insert(float (&lv)[K], int (&li)[K], float v, int c) {
+#pragma unroll
+  for (int j = K - 1; j > 0; --j) {
+    const bool up = v > lv[j - 1];  // v goes above slot j-1, whose entry moves down to j
+    const bool here = v > lv[j];
+    li[j] = up ? li[j - 1] : (here ? c : li[j]);
+    lv[j] = up ? lv[j - 1] : (here ? v : lv[j]);
+  }
+  if (v > lv[0]) { lv[0] = v; li[0] = c; }
+}
+
+// VEC: 16-B loads over the vectors that hold a column < NC (ld % 8 == 0, 16-B aligned), U in
+// flight as in topk_kernel, columns >= NC masked to -inf (no candidate, exp() = 0).
+template <int K, bool VEC, int U>
+__global__ __launch_bounds__(256) void topk_predict_kernel(const bf16_t* __restrict__ logits,
+                                                            int NC, int ld, int k,
+                                                            int* __restrict__ idx,
+                                                            float* __restrict__ prob) {
+  const int row = blockIdx.x;
+  const bf16_t* x = logits + (size_t)row * ld;
+  float m = -INFINITY, s = 0.f;
+  float lv[K];
+  int li[K];
+#pragma unroll
+  for (int j = 0; j < K; ++j) { lv[j] = -INFINITY; li[j] = TOP_NONE; }
+  if constexpr (VEC) {
+    const int nv = (NC + 7) / 8;
+    for (int i0 = threadIdx.x; i0 < nv; i0 += 256 * U) {
+      uint4 v[U];
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const int i = i0 + u * 256;
+        v[u] = i < nv ? *(const uint4*)(x + (size_t)i * 8) : make_uint4(0u, 0u, 0u, 0u);
+      }
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const int c0 = (i0 + u * 256) * 8;
+        if (c0 >= NC) continue;
+        float f[8];
+        unpack8(v[u], f);
+        float lm = -INFINITY;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          if (c0 + j >= NC) f[j] = -INFINITY;
+          lm = fmaxf(lm, f[j]);  // (skips NaN)
+        }
+        if (lm == -INFINITY) continue;  // no candidate here, and nothing for the sum
+        const float mn = fmaxf(m, lm);
+        float acc = s * __expf(m - mn);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) acc += __expf(f[j] - mn);
+        m = mn;
+        s = acc;
+        if (lm > lv[K - 1]) {
+#pragma unroll
+          for (int j = 0; j < 8; ++j)
+            if (f[j] > lv[K - 1]) top_insert<K>(lv, li, f[j], c0 + j);
+        }
+      }
+    }
+  } else {
+    for (int c = threadIdx.x; c < NC; c += 256) {
+      const float v = bf2f(x[c]);
+      lse_merge(m, s, v, 1.f);
+      if (v > lv[K - 1]) top_insert<K>(lv, li, v, c);  // (false for a NaN)
+    }
+  }
+  // the row's log-sum-exp, in ce_row_finish's order
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float m2 = __shfl_xor(m, o, 64), s2 = __shfl_xor(s, o, 64);
+    lse_merge(m, s, m2, s2);
+  }
+  __shared__ float sm[4], ss[4];
+  __shared__ float sv[K][4];
+  __shared__ int si[K][4];
+  const int w = threadIdx.x >> 6;
+  const bool lead = (threadIdx.x & 63) == 0;
+  if (lead) { sm[w] = m; ss[w] = s; }
+  // sm / ss are published by round 0's barrier and read by thread 0 alone, which keeps the
+  // row's lse for every round
+  float lse = 0.f;
+  for (int r = 0; r < k; ++r) {
+    float bv = lv[0];
+    int bi = li[0];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      const float v2 = __shfl_xor(bv, o, 64);
+      const int i2 = __shfl_xor(bi, o, 64);
+      if (top_outranks(v2, i2, bv, bi)) { bv = v2; bi = i2; }
+    }
+    if (lead) { sv[r][w] = bv; si[r][w] = bi; }
+    __syncthreads();
+    bv = sv[r][0]; bi = si[r][0];
+#pragma unroll
+    for (int i = 1; i < 4; ++i)
+      if (top_outranks(sv[r][i], si[r][i], bv, bi)) { bv = sv[r][i]; bi = si[r][i]; }
+    if (li[0] == bi) {  // column indices are unique: one lane (or, with none left, any empty one)
+#pragma unroll
+      for (int j = 0; j + 1 < K; ++j) { lv[j] = lv[j + 1]; li[j] = li[j + 1]; }
+      lv[K - 1] = -INFINITY; li[K - 1] = TOP_NONE;
+    }
+    if (threadIdx.x == 0) {
+      if (r == 0) {
+        float M = sm[0], S = ss[0];
+        for (int i = 1; i < 4; ++i) lse_merge(M, S, sm[i], ss[i]);
+        lse = M + __logf(S);
+      }
+      const bool some = bi != TOP_NONE;
+      idx[(size_t)row * k + r] = some ? bi : -1;
+      // (the sum's rounding can leave lse a few ulps under the largest logit)
+      prob[(size_t)row * k + r] = some ? fminf(__expf(bv - lse), 1.f) : 0.f;
+    }
+  }
+}
+
 // loss = sum of the per-row terms in a FIXED order (strided per-thread partial sums, then a
 // fixed tree): bitwise reproducible, unlike one float atomic per row (whose order varies
 // between launches), and one launch like the memset it replaces.
@@ -625,6 +767,28 @@ void topk_correct(const bf16_raw* logits, const int64_t* labels, int B, int NC, 
   else
     hipLaunchKernelGGL((topk_kernel<false, 1>), dim3(B), dim3(256), 0, s, logits, labels, NC, ld,
                        k, (unsigned long long*)count);
+}
+
+template <int K>
+static void topk_predict_k(const bf16_raw* logits, int B, int NC, int ld, int k, int* idx,
+                           float* prob, hipStream_t s) {
+  if (ld % 8 == 0 && ld >= NC && reinterpret_cast<uintptr_t>(logits) % 16 == 0)
+    hipLaunchKernelGGL((topk_predict_kernel<K, true, 4>), dim3(B), dim3(256), 0, s, logits, NC,
+                       ld, k, idx, prob);
+  else
+    hipLaunchKernelGGL((topk_predict_kernel<K, false, 1>), dim3(B), dim3(256), 0, s, logits, NC,
+                       ld, k, idx, prob);
+}
+
+// idx int32 [B][k], prob fp32 [B][k], 1 <= k <= 16: the lanes' lists hold the next
+// instantiated size (1, 5, 8 or 16)
+void topk_predict(const bf16_raw* logits, int B, int NC, int ld, int k, int* idx, float* prob,
+                  hipStream_t s) {
+  if (B <= 0) return;
+  if (k <= 1) topk_predict_k<1>(logits, B, NC, ld, k, idx, prob, s);
+  else if (k <= 5) topk_predict_k<5>(logits, B, NC, ld, k, idx, prob, s);
+  else if (k <= 8) topk_predict_k<8>(logits, B, NC, ld, k, idx, prob, s);
+  else topk_predict_k<16>(logits, B, NC, ld, k, idx, prob, s);
 }
 
 }  // namespace mpa

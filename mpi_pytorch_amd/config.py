@@ -110,6 +110,8 @@ class Config:
     eval_assign: str = "random"            # random (reference) | roundrobin
     eval_topk: int = 0                     # also report top-k accuracy (0 or 1: top-1 only)
     eval_src: int = 0                      # synthetic eval source side (0: the model input size)
+    predictions_csv: str = ""              # evaluation pipeline: write Id,Predicted,Probability here
+    predict_topk: int = 1                  # ... with the k best classes per row (1..16)
     max_steps: int = 0                     # stop an epoch early (0 = full epoch)
     checksum_every: int = 0                # cross-rank replica checksum period (steps, 0=off)
     timeout_s: float = 1800.0              # rendezvous/collective timeout
@@ -153,6 +155,8 @@ class Config:
             raise ValueError("ema_decay must be in [0, 1) (0 = off)")
         if self.eval_topk < 0:
             raise ValueError("eval_topk must be >= 0 (0 or 1 = top-1 only)")
+        if not 1 <= self.predict_topk <= 16:
+            raise ValueError("predict_topk must be in [1, 16]")
 
     # -----------------------------------------------------------------------------------
     @property

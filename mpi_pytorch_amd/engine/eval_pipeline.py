@@ -29,7 +29,9 @@ predictor fan-out across GPUs.  The CPU path runs the same stages without stream
 """
 from __future__ import annotations
 
+import csv
 import os
+import tempfile
 import time
 import threading
 from concurrent.futures import ThreadPoolExecutor
@@ -44,7 +46,8 @@ from ..data.loader import IMAGENET_MEAN, IMAGENET_STD
 from ..data.manifest import SyntheticImages, FolderImages, images_available, synthetic_manifest
 from ..models import initialize_model, input_spec
 from ..ops import functional as Fn
-from ..parallel import init_world, reduce_scalar, shard_dataframe, broadcast_object, ParamArena
+from ..parallel import (init_world, reduce_scalar, shard_dataframe, broadcast_object,
+                        all_gather_object, ParamArena)
 from ..parallel.comm import mpi_all_reduce
 from ..metrics import macro_scores
 from ..utils.logging import init_logger
@@ -75,7 +78,7 @@ def load_predictor(cfg: Config, device, ckpt_path: Optional[str] = None):
 class StreamPipeline:
     def __init__(self, model, device, out_hw, lanes: int = 1, depth: int = 4,
                  assign: str = "random", seed: int = 0, mode: int = 1, cpad=None, pad=None,
-                 topk: int = 0, macro: bool = False):
+                 topk: int = 0, macro: bool = False, predict_k: int = 0):
         self.model = model
         if cpad is None:  # the model stem's input layout (models.input_spec)
             spec = input_spec(model, out_hw)
@@ -106,6 +109,14 @@ class StreamPipeline:
         # when the head's width is known)
         self.macro = bool(macro)
         self.stats = [None] * self.lanes if self.macro else []
+        # predict_k > 0: the k best classes of every row of the shard and their probabilities,
+        # int32 / float32 [rows, k] on the device (made by ``run`` / ``run_ring``, which take
+        # the row count).  A lane writes its batch's rows [lo, lo + n) on its own stream:
+        # disjoint windows, so no lane count or assignment changes a bit
+        self.predict_k = int(predict_k)
+        if self.predict_k and not 1 <= self.predict_k <= 16:
+            raise ValueError("predict_k must be in [1, 16] (0 = off), got %r" % (predict_k,))
+        self.pred_idx = self.pred_prob = None
         self.seen = [0] * self.lanes
         self._pinned = {}
         self._last_slot = None
@@ -120,6 +131,35 @@ class StreamPipeline:
             Fn.count_correct(out, labels, self.counts[lane])
         if self.topk:
             Fn.count_topk(out, labels, self.topk, self.topk_counts[lane])
+
+    def _alloc_predictions(self, rows: Optional[int]) -> None:
+        if not self.predict_k:
+            return
+        if rows is None:
+            raise ValueError("predict_k > 0: run / run_ring need the shard's row count (rows=)")
+        self.pred_idx = torch.full((rows, self.predict_k), -1, dtype=torch.int32,
+                                   device=self.device)
+        self.pred_prob = torch.zeros(rows, self.predict_k, dtype=torch.float32,
+                                     device=self.device)
+        if self.cuda:  # the fills above run on the current stream
+            filled = torch.cuda.Event()
+            filled.record()
+            for s in self.lane_streams:
+                s.wait_event(filled)
+
+    def _predict(self, out, lo: int) -> None:
+        """Rows [lo, lo + n) of the prediction arrays from the batch's logits."""
+        n = out.shape[0]
+        Fn.predict_topk(out, self.predict_k, self.pred_idx[lo:lo + n],
+                        self.pred_prob[lo:lo + n])
+
+    def predictions(self):
+        """(class ids int32 [rows, k], probabilities float32 [rows, k]) as host arrays in the
+        order of the shard's rows, -1 / 0 in empty slots (None unless ``predict_k > 0`` and a
+        run was made); call after a run."""
+        if self.pred_idx is None:
+            return None
+        return self.pred_idx.cpu().numpy(), self.pred_prob.cpu().numpy()
 
     def topk_correct(self) -> List[int]:
         """Per-lane top-k correct counts (empty unless ``topk > 1``); call after a run."""
@@ -183,9 +223,12 @@ class StreamPipeline:
         return x, ev
 
     @torch.no_grad()
-    def run(self, batches) -> List[int]:
-        """``batches`` yields (uint8 images, int64 labels); returns per-lane correct counts."""
+    def run(self, batches, rows: Optional[int] = None) -> List[int]:
+        """``batches`` yields (uint8 images, int64 labels); returns per-lane correct counts.
+        ``rows``: the number of images in all (needed with ``predict_k``)."""
+        self._alloc_predictions(rows)
         inflight = []
+        lo = 0
         for i, (imgs, labels) in enumerate(batches):
             x, ev = self._preprocess(imgs)
             lane = self._lane_for(i)
@@ -197,6 +240,8 @@ class StreamPipeline:
                     y = labels.pin_memory().to(self.device, non_blocking=True)
                     out = self.model(x)
                     self._count(out, y, lane)
+                    if self.predict_k:
+                        self._predict(out, lo)
                     done = torch.cuda.Event()
                     done.record(s)
                 inflight.append(done)
@@ -205,18 +250,21 @@ class StreamPipeline:
             else:
                 out = self.model(x)
                 self._count(out, labels, lane)
+                if self.predict_k:
+                    self._predict(out, lo)
             self.seen[lane] += int(labels.shape[0])
+            lo += int(labels.shape[0])
         if self.cuda:
             for s in self.lane_streams:
                 s.synchronize()
         return [int(c.item()) for c in self.counts]
 
-
-
     @torch.no_grad()
-    def run_ring(self, ring, nbatches: int) -> List[int]:
+    def run_ring(self, ring, nbatches: int, rows: Optional[int] = None) -> List[int]:
         """GPU stages fed by a native ``BatchRing``: no per-batch host copy, pinning or
-        Python image work on the consumer thread.  Returns per-lane correct counts."""
+        Python image work on the consumer thread.  Returns per-lane correct counts.
+        ``rows``: the number of images in all (needed with ``predict_k``)."""
+        self._alloc_predictions(rows)
         pending = []   # (slot, copy event): the slot returns to the ring once copied
         inflight = []  # lane completion events (bounds the batches in flight)
         depth = ring.depth()
@@ -229,7 +277,7 @@ class StreamPipeline:
                 else:
                     keep.append((slot, ev))
             pending = keep
-            slot, img_h, lab_h, _bidx = ring.acquire()
+            slot, img_h, lab_h, bidx = ring.acquire()
             n, ext_h = ring.info(slot)
             ext = ext_h[:n].numpy().copy()
             uniform = bool((ext[:, 0] == img_h.shape[1]).all() and (ext[:, 1] == img_h.shape[2]).all())
@@ -254,6 +302,8 @@ class StreamPipeline:
                 lab_d.record_stream(s)
                 out = self.model(x)
                 self._count(out, lab_d, lane)
+                if self.predict_k:  # the ring hands batches out in index order
+                    self._predict(out, bidx * img_h.shape[0])
                 done = torch.cuda.Event()
                 done.record(s)
             inflight.append(done)
@@ -399,7 +449,10 @@ def run_pipeline(cfg: Config, ckpt_path: Optional[str] = None, max_images: int =
     shard = shard_dataframe(df, world.world_size)[world.rank]
     out_hw = cfg.input_hw if cfg.MODEL_NAME != "inception" else (299, 299)
     names = list(shard["file_name"].values)
-    labels = list(shard["category_id"].values)
+    # a manifest without labels (a real test set): every label is -1, which the counting
+    # kernels ignore, and no accuracy is reported
+    labelled = "category_id" in df.columns
+    labels = list(shard["category_id"].values) if labelled else [-1] * len(names)
     if not cfg.synthetic and images_available(cfg.TRAIN_DIR, names):
         source = FolderImages(cfg.TRAIN_DIR, cfg.num_workers)  # reads TRAIN_DIR like :59
     else:
@@ -411,7 +464,8 @@ def run_pipeline(cfg: Config, ckpt_path: Optional[str] = None, max_images: int =
         source = SyntheticImages((side, side) if side > 0 else tuple(out_hw))
     model = load_predictor(cfg, world.device, ckpt_path)
     pipe = StreamPipeline(model, world.device, out_hw, cfg.eval_lanes, assign=cfg.eval_assign,
-                          seed=cfg.seed + world.rank, topk=cfg.eval_topk, macro=cfg.eval_macro)
+                          seed=cfg.seed + world.rank, topk=cfg.eval_topk, macro=cfg.eval_macro,
+                          predict_k=cfg.predict_topk if cfg.predictions_csv else 0)
     t0 = time.perf_counter()
     if world.device.type == "cuda":
         pitch = None
@@ -421,7 +475,7 @@ def run_pipeline(cfg: Config, ckpt_path: Optional[str] = None, max_images: int =
         ring, nb = make_ring(names, labels, cfg.eval_batch, source, cfg.NUM_CLASSES,
                              threads=max(2, cfg.num_workers), pitch=pitch)
         try:
-            counts = pipe.run_ring(ring, nb)
+            counts = pipe.run_ring(ring, nb, rows=len(names))
         except RuntimeError as e:
             fe = feed_error(ring)
             if fe is not None:
@@ -431,7 +485,7 @@ def run_pipeline(cfg: Config, ckpt_path: Optional[str] = None, max_images: int =
             ring.stop()
             _FEED_ERRORS.pop(id(ring), None)
     else:
-        counts = pipe.run(_batches(names, labels, cfg.eval_batch, source))
+        counts = pipe.run(_batches(names, labels, cfg.eval_batch, source), rows=len(names))
     dt = time.perf_counter() - t0
     acc_local = 0.0
     for lane, c in enumerate(counts):
@@ -443,13 +497,19 @@ def run_pipeline(cfg: Config, ckpt_path: Optional[str] = None, max_images: int =
     if pipe.topk:
         total_k = reduce_scalar(sum(pipe.topk_correct()) / max(dataset_size, 1), root=0)
     macro = macro_scores(global_class_stats(pipe, cfg.NUM_CLASSES)) if pipe.macro else None
+    # shard_dataframe's shards are contiguous: the ranks' arrays, in rank order, are the
+    # manifest's rows in order
+    parts = all_gather_object(pipe.predictions()) if pipe.predict_k else None
     if world.rank == 0:
-        log.info("Accuracy is {}".format(total))
-        if pipe.topk:
-            log.info("Top-{} accuracy is {}".format(pipe.topk, total_k))
-        if macro is not None:
-            log.info("Macro-F1 is {}".format(macro["macro_f1"]))
-            log.info("Balanced accuracy is {}".format(macro["balanced_acc"]))
+        if not labelled:
+            log.info("No labels in {}: accuracy not computed".format(cfg.TEST_CSV))
+        else:
+            log.info("Accuracy is {}".format(total))
+            if pipe.topk:
+                log.info("Top-{} accuracy is {}".format(pipe.topk, total_k))
+            if macro is not None:
+                log.info("Macro-F1 is {}".format(macro["macro_f1"]))
+                log.info("Balanced accuracy is {}".format(macro["balanced_acc"]))
         # the source extent is part of the number: a synthetic source at the model's input
         # size skips the downscale real ~1000x677 herbarium JPEGs need (cfg.eval_src)
         src = "real images" if isinstance(source, FolderImages) else \
@@ -457,7 +517,49 @@ def run_pipeline(cfg: Config, ckpt_path: Optional[str] = None, max_images: int =
         log.info("_Throughput: {:.1f} img/s ({} images, {} lanes x {} ranks, {})".format(
             dataset_size / dt if dt > 0 else 0.0, dataset_size, pipe.lanes, world.world_size,
             src))
+        if parts is not None:
+            ids = df["id" if "id" in df.columns else "file_name"].values
+            write_predictions(cfg.predictions_csv, ids, np.concatenate([p[0] for p in parts]),
+                              np.concatenate([p[1] for p in parts]))
+            log.info("Predictions written to {} ({} rows, top-{})".format(
+                cfg.predictions_csv, len(ids), pipe.predict_k))
+    if not labelled:
+        return float("nan")
     return float(total) if total is not None else acc_local
+
+
+def write_predictions(path: str, ids, idx: np.ndarray, prob: np.ndarray) -> None:
+    """The predictions file: a header ``Id,Predicted,Probability`` (then ``Predicted_j,
+    Probability_j`` for j = 2..k) and one row per id; class ids are integers (-1: an empty
+    slot) and probabilities ``%.9g``, which a float32 survives.  Written to a temporary file
+    in the same directory and moved into place, so a crash leaves no truncated file."""
+    n, k = idx.shape
+    if len(ids) != n or prob.shape != idx.shape:
+        raise ValueError("write_predictions: {} ids, idx {}, prob {}".format(
+            len(ids), idx.shape, prob.shape))
+    header = ["Id", "Predicted", "Probability"]
+    for j in range(2, k + 1):
+        header += ["Predicted_%d" % j, "Probability_%d" % j]
+    d = os.path.dirname(os.path.abspath(path))
+    os.makedirs(d, exist_ok=True)
+    fd, tmp = tempfile.mkstemp(prefix="tmp_pred_", suffix=".csv", dir=d)
+    try:
+        with os.fdopen(fd, "w", newline="") as fh:
+            w = csv.writer(fh, lineterminator="\n")
+            w.writerow(header)
+            for i in range(n):
+                row = [ids[i]]
+                for j in range(k):
+                    row += [int(idx[i, j]), "%.9g" % float(prob[i, j])]
+                w.writerow(row)
+        # mkstemp made the file owner-only; give it the mode a plain open() would have
+        umask = os.umask(0)
+        os.umask(umask)
+        os.chmod(tmp, 0o666 & ~umask)
+        os.replace(tmp, path)
+    finally:
+        if os.path.exists(tmp):
+            os.remove(tmp)
 
 
 @torch.no_grad()
@@ -476,3 +578,28 @@ def plain_eval(model, names, labels, batch, source, device, out_hw, mode=1) -> i
                           out_dtype=torch.float32, pad=spec["pad"], extents=ext)
         Fn.count_correct(model(x), lab.to(device), correct)
     return int(correct.item())
+
+
+@torch.no_grad()
+def plain_predict(model, names, batch, source, device, out_hw, k: int, mode=1):
+    """Non-pipelined batched prediction (oracle for the pipeline's ``predictions()``): the
+    same two host arrays from one preprocess + forward + ``predict_topk`` per batch on the
+    current stream, with the pipeline's preprocess arguments (the model's input layout; bf16
+    on the GPU, fp32 on the CPU)."""
+    device = torch.device(device)
+    spec = input_spec(model, out_hw)
+    dtype = {} if device.type == "cuda" else {"out_dtype": torch.float32}
+    idx = torch.full((len(names), k), -1, dtype=torch.int32, device=device)
+    prob = torch.zeros(len(names), k, dtype=torch.float32, device=device)
+    lo = 0
+    for imgs, _lab in _batches(names, [-1] * len(names), batch, source):
+        ext = None
+        if not isinstance(imgs, np.ndarray):
+            imgs, ext = pad_batch(imgs)
+        g = torch.from_numpy(imgs).to(device)
+        x = Fn.preprocess(g, out_hw, IMAGENET_MEAN, IMAGENET_STD, mode, spec["cpad"],
+                          pad=spec["pad"], extents=ext, **dtype)
+        n = x.shape[0]
+        Fn.predict_topk(model(x), k, idx[lo:lo + n], prob[lo:lo + n])
+        lo += n
+    return idx.cpu().numpy(), prob.cpu().numpy()

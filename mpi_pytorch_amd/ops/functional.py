@@ -1381,6 +1381,23 @@ def count_topk(logits, labels, k: int, count: torch.Tensor) -> None:
     K(logits).topk_correct(logits, labels, int(k), count)
 
 
+def predict_topk(logits, k: int, idx: Optional[torch.Tensor] = None,
+                 prob: Optional[torch.Tensor] = None):
+    """The k (1..16) best classes of every row and their softmax probabilities, in one pass
+    over the logits: ``idx`` int32 [B, k] in ``count_topk``'s order (ties to the lower index,
+    -1 past the last class that is neither NaN nor -inf) and ``prob`` float32 [B, k].  Given
+    tensors (row windows of larger buffers, say) are written; missing ones are allocated.
+    Returns (idx, prob)."""
+    k = int(k)
+    B = logits.shape[0]
+    if idx is None:
+        idx = torch.empty(B, max(k, 0), dtype=torch.int32, device=logits.device)
+    if prob is None:
+        prob = torch.empty(B, max(k, 0), dtype=torch.float32, device=logits.device)
+    K(logits).topk_predict(logits, k, idx, prob)
+    return idx, prob
+
+
 def preprocess(img_u8, out_hw, mean, std, mode: int = 0, cpad: int = 3,
                out_dtype=torch.bfloat16, pad=None, extents=None, boxes=None, mix=None, lam=None):
     """u8 [B,H,W,3] -> resized, normalized NHWC with ``cpad`` channels, optionally on a

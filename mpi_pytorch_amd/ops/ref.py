@@ -654,6 +654,38 @@ def topk_correct(logits, labels, k, count):
     count.add_(ok.sum().to(count.dtype))
 
 
+def topk_predict(logits, k, idx, prob):
+    """The k best classes of every row and their softmax probabilities, written into ``idx``
+    int32 [B, k] and ``prob`` float32 [B, k].  Candidates are the columns whose logit is
+    neither NaN nor -inf; c outranks d when x[c] > x[d], or x[c] == x[d] and c < d
+    (``topk_correct``'s order), and idx[r, j] is the candidate that exactly j candidates
+    outrank.  prob[r, j] = exp(x[idx] - logsumexp(x[r])); slots past the last candidate get
+    idx = -1 and prob = 0.  (With a NaN or +inf in the row its probabilities are unspecified.)"""
+    if not 1 <= k <= 16:
+        raise ValueError("topk_predict: k must be in [1, 16], got %r" % (k,))
+    B, NC = logits.shape
+    for t, dt, what in ((idx, torch.int32, "idx"), (prob, torch.float32, "prob")):
+        if (t.dtype != dt or tuple(t.shape) != (B, k) or not t.is_contiguous()
+                or t.device != logits.device):
+            raise ValueError("topk_predict: %s must be a contiguous %s [B, k] tensor on the "
+                             "logits' device" % (what, dt))
+    lf = _f(logits)
+    ninf = torch.full_like(lf, float("-inf"))
+    v, order = torch.sort(torch.where(torch.isnan(lf), ninf, lf), dim=1, descending=True,
+                          stable=True)  # stable: equal logits keep their column order
+    n = min(k, NC)
+    v, order = v[:, :n], order[:, :n]
+    some = v > float("-inf")
+    # row by row: a batched reduction may split a long row differently from batch to batch,
+    # and a row's outputs depend on that row alone
+    lse = torch.stack([torch.logsumexp(row, 0) for row in lf]) if B else lf.new_zeros(0)
+    p = torch.exp(v - lse[:, None]).clamp(max=1.0)
+    idx.fill_(-1)
+    prob.zero_()
+    idx[:, :n] = torch.where(some, order, torch.full_like(order, -1)).to(torch.int32)
+    prob[:, :n] = torch.where(some, p, torch.zeros_like(p))
+
+
 # ----------------------------------------------------------------------------- optimizer
 def adam_step(master, grad, m, v, shadow, step_t, lr, b1, b2, eps, wd, grad_scale):
     step = float(step_t.item()) + 1.0
