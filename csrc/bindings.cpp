@@ -500,6 +500,87 @@ void conv_wgrad(Tensor dy, Tensor x, Tensor dw, int64_t sh, int64_t sw, int64_t 
   mpa::igemm_wgrad(a, vec_width(K), (C % 8 == 0) ? 8 : 1, cur_stream());
 }
 
+// ---------------------------------------------------------------------- depthwise conv
+// x [N, H, W, C] bf16, w [C, k, k, 1] bf16 (layers.Conv2d groups == C); k in {3, 5}, one stride
+// in {1, 2} for both directions, padding k / 2: anything else is refused, not served slowly
+static mpa::DwGeom dw_geom(const char* op, const Tensor& w, int64_t N, int64_t H, int64_t W,
+                           int64_t sh, int64_t sw, int64_t ph, int64_t pw) {
+  TORCH_CHECK(w.dim() == 4 && w.size(3) == 1 && w.size(1) == w.size(2), op,
+              ": w must be [C, k, k, 1]");
+  const int64_t k = w.size(1);
+  TORCH_CHECK(sh == sw && ph == pw && ph == k / 2, op,
+              ": one stride for both directions and padding k / 2, got stride (", sh, ", ", sw,
+              "), padding (", ph, ", ", pw, "), k = ", k);
+  TORCH_CHECK(N > 0 && N < (1 << 24) && H < (1 << 24) && W < (1 << 24), op, ": extent");
+  const mpa::DwGeom g{(int)N, (int)H, (int)W, (int)w.size(0), (int)k, (int)sh};
+  const char* err = mpa::dw_geom_error(g);
+  TORCH_CHECK(!err, op, ": ", err);
+  return g;
+}
+
+Tensor dwconv_fwd(Tensor x, Tensor w, int64_t sh, int64_t sw, int64_t ph, int64_t pw, Tensor stats,
+                  Tensor shift) {
+  CHECK_ACT(x);
+  CHECK_ACT(w);
+  TORCH_CHECK(x.dim() == 4 && x.size(3) == w.size(0) && aligned16(x),
+              "dwconv_fwd: x NHWC with w's channels, 16-byte aligned");
+  const mpa::DwGeom g = dw_geom("dwconv_fwd", w, x.size(0), x.size(1), x.size(2), sh, sw, ph, pw);
+  const int P = mpa::dw_out(g.H, g.k, g.s), Q = mpa::dw_out(g.W, g.k, g.s);
+  if (has(stats)) TORCH_CHECK(stats.numel() == 2 * g.C, "dwconv_fwd: stats size");
+  if (has(shift)) TORCH_CHECK(shift.numel() == g.C, "dwconv_fwd: shift size");
+  const c10::OptionalDeviceGuard guard(device_of(x));
+  Tensor z = empty_like_shape(x, {g.N, P, Q, g.C}, torch::kBFloat16);
+  float* st = fopt_mut(stats);
+  Tensor ws;
+  float* wsp = st ? alloc_ws(ws, x, mpa::dwconv_fwd_ws_floats(g)) : nullptr;
+  mpa::dwconv_fwd(bp(x), bp(w), g, bpm(z), st, st ? fopt(shift) : nullptr, wsp, cur_stream());
+  return z;
+}
+
+Tensor dwconv_dgrad(Tensor dy, Tensor w, int64_t H, int64_t W, int64_t sh, int64_t sw, int64_t ph,
+                    int64_t pw, c10::optional<Tensor> accum) {
+  CHECK_ACT(dy);
+  CHECK_ACT(w);
+  TORCH_CHECK(dy.dim() == 4 && dy.size(3) == w.size(0) && aligned16(dy),
+              "dwconv_dgrad: dy NHWC with w's channels, 16-byte aligned");
+  const mpa::DwGeom g = dw_geom("dwconv_dgrad", w, dy.size(0), H, W, sh, sw, ph, pw);
+  TORCH_CHECK(dy.size(1) == mpa::dw_out(g.H, g.k, g.s) && dy.size(2) == mpa::dw_out(g.W, g.k, g.s),
+              "dwconv_dgrad: dy is not the conv output of an H x W input");
+  const c10::OptionalDeviceGuard guard(device_of(dy));
+  const bool acc = accum && accum->defined();
+  Tensor dx;
+  if (acc) {
+    CHECK_ACT((*accum));
+    TORCH_CHECK(accum->dim() == 4 && accum->size(0) == g.N && accum->size(1) == H &&
+                    accum->size(2) == W && accum->size(3) == g.C && aligned16(*accum),
+                "dwconv_dgrad: accum shape mismatch");
+    dx = *accum;
+  } else {
+    dx = empty_like_shape(dy, {g.N, H, W, g.C}, torch::kBFloat16);
+  }
+  mpa::dwconv_dgrad(bp(dy), bp(w), g, bpm(dx), acc ? bp(dx) : nullptr, cur_stream());
+  return dx;
+}
+
+void dwconv_wgrad(Tensor dy, Tensor x, Tensor dw, int64_t sh, int64_t sw, int64_t ph, int64_t pw,
+                  bool overwrite) {
+  CHECK_ACT(dy);
+  CHECK_ACT(x);
+  CHECK_CUDA(dw);
+  CHECK_F32(dw);
+  CHECK_CONTIG(dw);
+  TORCH_CHECK(x.dim() == 4 && dy.dim() == 4 && x.size(3) == dw.size(0) && dy.size(3) == dw.size(0) &&
+                  dy.size(0) == x.size(0) && aligned16(x) && aligned16(dy),
+              "dwconv_wgrad: x, dy NHWC (16-byte aligned) with dw's channels and one batch");
+  const mpa::DwGeom g = dw_geom("dwconv_wgrad", dw, x.size(0), x.size(1), x.size(2), sh, sw, ph, pw);
+  TORCH_CHECK(dy.size(1) == mpa::dw_out(g.H, g.k, g.s) && dy.size(2) == mpa::dw_out(g.W, g.k, g.s),
+              "dwconv_wgrad: dy is not the conv output of x");
+  const c10::OptionalDeviceGuard guard(device_of(dy));
+  Tensor ws;
+  float* wsp = alloc_ws(ws, dy, mpa::dwconv_wgrad_ws_floats(g));
+  mpa::dwconv_wgrad(bp(dy), bp(x), g, dw.data_ptr<float>(), overwrite, wsp, cur_stream());
+}
+
 Tensor act_bwd(Tensor dy, Tensor y, Tensor dbias) {
   CHECK_ACT(dy);
   const int C = dy.size(-1);
@@ -2009,6 +2090,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("conv_wgrad", &conv_wgrad, py::arg("dy"), py::arg("x"), py::arg("dw"), py::arg("sh"),
         py::arg("sw"), py::arg("ph"), py::arg("pw"), py::arg("overwrite") = false,
         "weight gradient into dw (+=; overwrite: dw = ..., the first gradient since zero)");
+  m.def("dwconv_fwd", &dwconv_fwd, py::arg("x"), py::arg("w"), py::arg("sh"), py::arg("sw"),
+        py::arg("ph"), py::arg("pw"), py::arg("stats"), py::arg("shift"),
+        "depthwise conv forward (+ BN statistics of its output)");
+  m.def("dwconv_dgrad", &dwconv_dgrad, py::arg("dy"), py::arg("w"), py::arg("H"), py::arg("W"),
+        py::arg("sh"), py::arg("sw"), py::arg("ph"), py::arg("pw"), py::arg("accum") = py::none());
+  m.def("dwconv_wgrad", &dwconv_wgrad, py::arg("dy"), py::arg("x"), py::arg("dw"), py::arg("sh"),
+        py::arg("sw"), py::arg("ph"), py::arg("pw"), py::arg("overwrite") = false);
   m.def("conv_bnred_ok", &conv_bnred_ok);
   m.def("conv_dgrad_bnred_gacc", &conv_dgrad_bnred_gacc);
   m.def("conv_dgrad_res", &conv_dgrad_res);

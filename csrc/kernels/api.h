@@ -8,6 +8,7 @@
 #include <stdint.h>
 
 #include "igemm_args.h"
+#include "dw_plan.h"
 
 namespace mpa {
 
@@ -103,6 +104,22 @@ int active_cus();
 bool conv_stem_ok(const IGemmArgs& a);
 int conv_stem(IGemmArgs a, hipStream_t s);
 void igemm_set_stem(int on);  // MPA_STEM_DIRECT=0 disables (A/B, tests)
+
+// conv_dw.hip: depthwise conv (groups == C), NHWC bf16, weight [C][k][k], k in {3, 5}, stride
+// in {1, 2}, padding k / 2 (dw_geom_error(g) == nullptr); planned by dw_plan.h.  No float
+// atomics: every reduction is partial rows into ws, then a fixed-order sum.
+// fwd: stats (optional) receives [mean | var] [2][C] of the stored z, sums shifted by shift
+// (optional); ws holds dwconv_fwd_ws_floats(g) floats when stats is set
+int64_t dwconv_fwd_ws_floats(const DwGeom& g);
+void dwconv_fwd(const bf16_raw* x, const bf16_raw* w, const DwGeom& g, bf16_raw* z, float* stats,
+                const float* shift, float* ws, hipStream_t s);
+// dx [N][H][W][C] = dgrad(dy) (+ accum in fp32 before the one rounding; accum may be dx)
+void dwconv_dgrad(const bf16_raw* dy, const bf16_raw* w, const DwGeom& g, bf16_raw* dx,
+                  const bf16_raw* accum, hipStream_t s);
+// dw [C][k][k] fp32 (+)= weight gradient; ws holds dwconv_wgrad_ws_floats(g) floats
+int64_t dwconv_wgrad_ws_floats(const DwGeom& g);
+void dwconv_wgrad(const bf16_raw* dy, const bf16_raw* x, const DwGeom& g, float* dw,
+                  bool overwrite, float* ws, hipStream_t s);
 
 // bn.hip  (x/y/res/dy/dx: [M][C] bf16 rows; per-channel fp32 vectors)
 // ws: float workspace of bn_ws_floats(M, C) elements (per-block partial-sum slab)

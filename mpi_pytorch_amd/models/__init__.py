@@ -28,6 +28,7 @@ from .vgg import vgg11_bn, vgg16, alexnet, VGG, AlexNet
 from .squeezenet import squeezenet1_0, SqueezeNet
 from .densenet import densenet121, DenseNet
 from .inception import inception_v3, Inception3, InceptionOutputs
+from .mnasnet import mnasnet1_0, MNASNet
 
 ARCH = {
     "resnet18": ("resnet18", resnet18, 224),
@@ -38,6 +39,12 @@ ARCH = {
     "squeezenet": ("squeezenet1_0", squeezenet1_0, 224),
     "densenet": ("densenet121", densenet121, 224),
     "inception": ("inception_v3", inception_v3, 299),
+}
+
+# Architectures beyond the reference's model keys, with the same (arch, constructor, input
+# size) entries; ``initialize_model`` looks a name up in ARCH, then here.
+EXTRA_ARCH = {
+    "mnasnet": ("mnasnet1_0", mnasnet1_0, 224),
 }
 
 
@@ -60,9 +67,9 @@ def _maybe_pretrained(model: nn.Module, arch: str) -> None:
 
 def initialize_model(model_name: str, num_classes: int, feature_extract: bool,
                      use_pretrained: bool = False) -> Tuple[nn.Module, int]:
-    if model_name not in ARCH:
+    if model_name not in ARCH and model_name not in EXTRA_ARCH:
         raise ValueError("Invalid model name {!r}".format(model_name))
-    arch, ctor, input_size = ARCH[model_name]
+    arch, ctor, input_size = ARCH.get(model_name) or EXTRA_ARCH[model_name]
     model = ctor(1000)
     if use_pretrained:
         _maybe_pretrained(model, arch)
@@ -78,6 +85,8 @@ def initialize_model(model_name: str, num_classes: int, feature_extract: bool,
     elif model_name == "inception":
         model.AuxLogits.fc = Linear(model.AuxLogits.fc.in_features, num_classes)
         model.fc = Linear(model.fc.in_features, num_classes)
+    elif model_name == "mnasnet":
+        model.classifier[1] = Linear(model.classifier[1].in_features, num_classes)
     return model, input_size
 
 
@@ -100,7 +109,8 @@ def head_parameters(model: nn.Module):
             yield from m.parameters()
 
 
-__all__ = ["initialize_model", "set_parameter_requires_grad", "ARCH", "InceptionOutputs",
+__all__ = ["initialize_model", "set_parameter_requires_grad", "ARCH", "EXTRA_ARCH",
+           "InceptionOutputs", "mnasnet1_0",
            "input_spec",
            "resnet18", "resnet34", "vgg11_bn", "vgg16", "alexnet", "squeezenet1_0",
            "densenet121", "inception_v3"]

@@ -68,12 +68,24 @@ class Conv2d(nn.Module):
     """
 
     def __init__(self, in_channels: int, out_channels: int, kernel_size, stride=1, padding=0,
-                 bias: bool = True, pad_out: bool = False):
+                 bias: bool = True, pad_out: bool = False, groups: int = 1):
         super().__init__()
+        if groups != 1 and not (groups == in_channels == out_channels):
+            raise ValueError("Conv2d: groups must be 1 or in_channels == out_channels "
+                             "(depthwise), got groups={} for {} -> {} channels".format(
+                                 groups, in_channels, out_channels))
+        self.groups = groups
+        # depthwise: weight stored [C, R, S, 1] (OIHW [C, 1, R, S]), run by the dwconv kernels
+        # (Fn.dwconv); no channel padding, no pixel pairs, no transposed copy (the kernels
+        # transpose their channel chunk of the stored weight while staging it)
+        self.depthwise = groups != 1
+        self.cin_w = in_channels // groups  # the weight's input-channel extent
         self.in_channels = in_channels
         kh0, kw0 = _pair(kernel_size)
         self.pair = (_PAIR_STEM and in_channels <= 4 and _pair(stride)[1] == 2 and kw0 >= 2)
         self.cin_store = 8 if in_channels < 8 else in_channels
+        if self.depthwise:
+            self.pair, self.cin_store = False, 1
         self.out_channels = out_channels
         # pad_out: store the output channels rounded up to a multiple of 32 (zero filters) -
         # for classifier convs (SqueezeNet's 512 -> 64,500 1x1 head) so their dgrad / wgrad
@@ -89,16 +101,17 @@ class Conv2d(nn.Module):
             self.kgeom = (self.stride[0], 1, 0, 0)
         else:
             self.kgeom = (self.stride[0], self.stride[1], self.padding[0], self.padding[1])
-        w = torch.empty(out_channels, in_channels, kh, kw)
+        w = torch.empty(out_channels, self.cin_w, kh, kw)
         nn.init.kaiming_uniform_(w, a=math.sqrt(5))
         self.weight = nn.Parameter(self._imp(w).contiguous())
         self.weight._mpa_export = self._exp
         self.weight._mpa_import = self._imp
         # (K, R*S, C) of the stored KRSC weight: the arena keeps a [C][R*S][K] copy for dgrad
         ks = self.sp if self.pair else kw
-        self.weight._mpa_tlayout = (self.cout_store, kh * ks, self.cin_store)
+        if not self.depthwise:
+            self.weight._mpa_tlayout = (self.cout_store, kh * ks, self.cin_store)
         if bias:
-            fan_in = in_channels * kh * kw
+            fan_in = self.cin_w * kh * kw
             bound = 1 / math.sqrt(fan_in)
             b = torch.empty(out_channels).uniform_(-bound, bound)
             self.bias = nn.Parameter(self._imp_bias(b))
@@ -112,7 +125,7 @@ class Conv2d(nn.Module):
         if self.pair:  # [K][R][Sp][2 x 4] -> [K][R][S][3]
             kh, kw = self.kernel_size
             t = t.reshape(t.shape[0], kh, 2 * self.sp, 4)[:, :, :kw, :self.in_channels]
-        elif self.cin_store != self.in_channels:
+        elif self.cin_store != self.cin_w:
             t = t[..., :self.in_channels]
         if self.cout_store != self.out_channels:
             t = t[:self.out_channels]
@@ -124,7 +137,7 @@ class Conv2d(nn.Module):
             kh, kw = self.kernel_size
             t = F.pad(t, (0, 4 - self.in_channels, 0, 2 * self.sp - kw))
             t = t.reshape(t.shape[0], kh, self.sp, 8)
-        elif self.cin_store != self.in_channels:
+        elif self.cin_store != self.cin_w:
             t = F.pad(t, (0, self.cin_store - self.in_channels))
         if t.shape[0] < self.cout_store:
             t = F.pad(t, (0, 0, 0, 0, 0, 0, 0, self.cout_store - t.shape[0]))
@@ -139,7 +152,7 @@ class Conv2d(nn.Module):
     # init helpers operate in OIHW space so the distributions match torchvision
     def init_(self, fn) -> "Conv2d":
         with torch.no_grad():
-            w = torch.empty(self.out_channels, self.in_channels, *self.kernel_size)
+            w = torch.empty(self.out_channels, self.cin_w, *self.kernel_size)
             fn(w)
             self.weight.copy_(self._imp(w))
         return self
@@ -160,7 +173,7 @@ class Conv2d(nn.Module):
         k = prefix + "weight"
         if k in state_dict:
             w = state_dict[k]
-            if tuple(w.shape) == (self.out_channels, self.in_channels, *self.kernel_size):
+            if tuple(w.shape) == (self.out_channels, self.cin_w, *self.kernel_size):
                 state_dict[k] = self._imp(w)
         k = prefix + "bias"
         if k in state_dict and tuple(state_dict[k].shape) == (self.out_channels,):
@@ -169,6 +182,9 @@ class Conv2d(nn.Module):
                                       unexpected_keys, error_msgs)
 
     def forward(self, x, relu: bool = False):
+        if self.depthwise:
+            y = Fn.dwconv(x, self)
+            return ReLU()(y) if relu else y
         return Fn.conv_act(x, self, relu=relu)
 
     def input_spec(self, hw) -> dict:
@@ -213,9 +229,9 @@ class Conv2d(nn.Module):
             Fn.K(g).zero_cols_f32(g, self.sp * 8, (self.sp - 1) * 8 + 4, 4)
 
     def extra_repr(self):
-        return "{}, {}, kernel_size={}, stride={}, padding={}, bias={}".format(
+        return "{}, {}, kernel_size={}, stride={}, padding={}, bias={}{}".format(
             self.in_channels, self.out_channels, self.kernel_size, self.stride, self.padding,
-            self.bias is not None)
+            self.bias is not None, ", groups=%d" % self.groups if self.depthwise else "")
 
 
 class BatchNorm2d(nn.Module):

@@ -927,6 +927,73 @@ def conv_act(x, conv, relu: bool = False, join: Optional[GradJoin] = None,
                       _empty(x), _empty(x))
 
 
+# ======================================================================== depthwise conv
+class _DwConv(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, w, conv, stats=None, shift=None, join=None):
+        k = K(x)
+        sh, sw, ph, pw = conv.kgeom
+        z = k.dwconv_fwd(x, weight_of(w), sh, sw, ph, pw, _or_empty(stats, x),
+                         _or_empty(shift, x))
+        ctx.conv, ctx.w, ctx.join = conv, w, join
+        ctx.in_hw = (x.shape[1], x.shape[2])
+        ctx.save_for_backward(x)
+        return z
+
+    @staticmethod
+    def backward(ctx, dz):
+        (x,) = ctx.saved_tensors
+        w, conv = ctx.w, ctx.conv
+        k = K(dz)
+        dz = dz.contiguous()
+        if w.requires_grad:
+            sh, sw, ph, pw = conv.kgeom
+
+            def wgrad():
+                k.dwconv_wgrad(dz, x, w.grad, sh, sw, ph, pw, overwrite=_fresh(w))
+                _done(w)
+            _run_wgrad(wgrad, dz, x)
+        dx = None
+        if ctx.needs_input_grad[0]:
+            sh, sw, ph, pw = conv.kgeom
+            j = ctx.join
+            # a join's running partial, when it is a written tensor, is accumulated into by
+            # the kernel (fp32 add, one rounding); otherwise dx joins as a computed tensor
+            prev = j.partial if j is not None else None
+            if isinstance(prev, torch.Tensor) and prev.is_contiguous():
+                j.partial = None
+                dx = j.add(k, k.dwconv_dgrad(dz, weight_of(w), *ctx.in_hw, sh, sw, ph, pw, prev))
+            else:
+                dx = k.dwconv_dgrad(dz, weight_of(w), *ctx.in_hw, sh, sw, ph, pw)
+                if j is not None:
+                    dx = j.add(k, dx)
+        return _grads(_DwConv, dx)
+
+
+def dwconv(x, conv, stats: Optional[torch.Tensor] = None, shift: Optional[torch.Tensor] = None,
+           join: Optional[GradJoin] = None):
+    """Depthwise conv (``conv.groups == channels``, no bias); ``stats`` ([2, C] fp32): receives
+    the output's per-channel [mean | var] from the kernel's epilogue (sums shifted by ``shift``)
+    in the format ``bn_act(stats=)`` takes; ``join``: x's gradient is summed with its other
+    consumers' (GradJoin)."""
+    if not conv.depthwise or conv.bias is not None:
+        raise ValueError("dwconv: a bias-free depthwise Conv2d (groups == channels) expected")
+    if torch.is_grad_enabled() and (conv.weight.requires_grad or x.requires_grad):
+        return _DwConv.apply(x, conv.weight, conv, stats, shift, join)
+    sh, sw, ph, pw = conv.kgeom
+    return K(x).dwconv_fwd(x, weight_of(conv.weight), sh, sw, ph, pw, _or_empty(stats, x),
+                           _or_empty(shift, x))
+
+
+def dwconv_bn_act(x, conv, bn, relu: bool = True):
+    """relu?(bn(dwconv(x))): train mode takes the BN statistics from the conv's epilogue."""
+    if bn.training:
+        stats = torch.empty(2, conv.out_channels, device=x.device, dtype=torch.float32)
+        z = dwconv(x, conv, stats, None if _NO_SHIFT else bn.running_mean)
+        return bn_act(z, bn, relu=relu, stats=stats)
+    return bn_act(dwconv(x, conv), bn, relu=relu)
+
+
 # =========================================================================== standalone BN
 class _BNAct(torch.autograd.Function):
     @staticmethod

@@ -131,6 +131,46 @@ def conv_wgrad(dy, x, dw, sh, sw, ph, pw, overwrite=False):
         dw.add_(gw.permute(0, 2, 3, 1))
 
 
+# ------------------------------------------------------------------------- depthwise conv
+def _dw_oihw(w):
+    """Stored depthwise weight [C, R, S, 1] -> OIHW [C, 1, R, S] in fp32."""
+    return _f(w).permute(0, 3, 1, 2).contiguous()
+
+
+def dwconv_fwd(x, w, sh, sw, ph, pw, stats, shift=None):
+    C = x.shape[-1]
+    y = _nhwc(F.conv2d(_nchw(_f(x)), _dw_oihw(w), None, (sh, sw), (ph, pw), 1, C)).to(x.dtype)
+    st = _opt(stats)
+    if st is not None:  # finalized (mean, biased var) of the stored output
+        yf = y.float().reshape(-1, C)
+        st[0].copy_(yf.mean(0))
+        st[1].copy_(yf.var(0, unbiased=False))
+    return y
+
+
+def dwconv_dgrad(dy, w, H, W, sh, sw, ph, pw, accum=None):
+    N, C = dy.shape[0], dy.shape[3]
+    gi = torch.ops.aten.convolution_backward(
+        _nchw(_f(dy)).contiguous(), torch.empty(N, C, H, W, device=dy.device), _dw_oihw(w), None,
+        [sh, sw], [ph, pw], [1, 1], False, [0, 0], C, [True, False, False])[0]
+    if accum is not None:
+        accum.copy_((_f(accum) + _nhwc(gi)).to(accum.dtype))
+        return accum
+    return _nhwc(gi).to(dy.dtype)
+
+
+def dwconv_wgrad(dy, x, dw, sh, sw, ph, pw, overwrite=False):
+    C, R, S, _ = dw.shape
+    gw = torch.ops.aten.convolution_backward(
+        _nchw(_f(dy)).contiguous(), _nchw(_f(x)).contiguous(),
+        torch.empty(C, 1, R, S, device=dy.device), None, [sh, sw], [ph, pw], [1, 1], False,
+        [0, 0], C, [False, True, False])[1]
+    if overwrite:
+        dw.copy_(gw.permute(0, 2, 3, 1))
+    else:
+        dw.add_(gw.permute(0, 2, 3, 1))
+
+
 def act_bwd(dy, y, dbias):
     """g = dy * (y > 0) if y given else dy; dbias += sum_rows(g)."""
     g = dy if _opt(y) is None else (_f(dy) * (_f(y) > 0)).to(dy.dtype)
