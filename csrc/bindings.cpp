@@ -581,6 +581,174 @@ void dwconv_wgrad(Tensor dy, Tensor x, Tensor dw, int64_t sh, int64_t sw, int64_
   mpa::dwconv_wgrad(bp(dy), bp(x), g, dw.data_ptr<float>(), overwrite, wsp, cur_stream());
 }
 
+// ------------------------------------------------- squeeze-excite / activation gate (se.hip)
+// z / du [N, H, W, C] bf16 (or [B, C]: one "image" of B pixels), aff [2, C] fp32, act 0 | 1 | 2;
+// per-image operands (gate, dpool, pooled, ...) [N, C] fp32.  Anything else is refused.
+static mpa::SeGeom se_geom(const char* op, const Tensor& z, const Tensor& aff, int64_t act) {
+  CHECK_ACT(z);
+  TORCH_CHECK(z.dim() == 4 || z.dim() == 2, op, ": z must be [N, H, W, C] or [B, C]");
+  TORCH_CHECK(act >= 0 && act <= 2, op, ": act must be 0 (identity), 1 (ReLU) or 2 (hardswish)");
+  const int64_t C = z.size(-1), N = z.dim() == 4 ? z.size(0) : 1;
+  TORCH_CHECK(z.numel() < ((int64_t)1 << 31), op, ": tensor too large (2^31 elements)");
+  const mpa::SeGeom g{(int)N, (int)(C > 0 && N > 0 ? z.numel() / (N * C) : 0), (int)C};
+  const char* err = mpa::se_geom_error(g);
+  TORCH_CHECK(!err, op, ": ", err);
+  TORCH_CHECK(aligned16(z), op, ": z must be 16-byte aligned");
+  CHECK_CUDA(aff);
+  TORCH_CHECK(aff.scalar_type() == torch::kFloat32 && aff.is_contiguous() && aff.numel() == 2 * C,
+              op, ": aff [2, C] fp32");
+  return g;
+}
+
+// optional [rows, C] fp32 operand of an se op (empty: absent)
+static const float* se_vec(const char* op, const char* name, const Tensor& t, int64_t rows,
+                           int64_t C) {
+  if (!has(t)) return nullptr;
+  TORCH_CHECK(t.numel() == rows * C, op, ": ", name, " must hold ", rows, " x ", C, " floats");
+  return fopt(t);
+}
+
+static void se_same(const char* op, const Tensor& du, const Tensor& z) {
+  CHECK_ACT(du);
+  TORCH_CHECK(du.sizes() == z.sizes() && aligned16(du), op, ": du must have z's shape");
+}
+
+Tensor act_pool(Tensor z, Tensor aff, int64_t act) {
+  const mpa::SeGeom g = se_geom("act_pool", z, aff, act);
+  const c10::OptionalDeviceGuard guard(device_of(z));
+  Tensor pooled = empty_like_shape(z, {g.N, g.C}, torch::kFloat32);
+  Tensor ws;
+  float* wsp = alloc_ws(ws, z, mpa::se_ws_floats(g, g.C));
+  mpa::act_pool(bp(z), aff.data_ptr<float>(), (int)act, g, pooled.data_ptr<float>(), wsp,
+                cur_stream());
+  return pooled;
+}
+
+// the SE layer's fc weights: w1 [Cs, (1, 1,) C], w2 [C, (1, 1,) Cs] bf16
+static void se_fc_check(const char* op, const Tensor& w1, const Tensor& w2, int64_t N, int64_t C,
+                        int64_t Cs) {
+  CHECK_ACT(w1);
+  CHECK_ACT(w2);
+  TORCH_CHECK(w1.size(0) == Cs && w1.numel() == Cs * C && w2.size(0) == C && w2.numel() == C * Cs &&
+                  aligned16(w1) && aligned16(w2),
+              op, ": w1 [Cs, C] and w2 [C, Cs] expected (16-byte aligned)");
+  const char* err = mpa::se_gate_error((int)N, (int)C, (int)Cs);
+  TORCH_CHECK(!err, op, ": ", err);
+}
+
+std::vector<Tensor> se_gate(Tensor pooled, Tensor w1, Tensor b1, Tensor w2, Tensor b2) {
+  CHECK_CUDA(pooled);
+  CHECK_F32(pooled);
+  CHECK_CONTIG(pooled);
+  TORCH_CHECK(pooled.dim() == 2 && w1.dim() >= 2 && w2.dim() >= 2, "se_gate: pooled [N, C]");
+  const int64_t N = pooled.size(0), C = pooled.size(1), Cs = w1.size(0);
+  se_fc_check("se_gate", w1, w2, N, C, Cs);
+  TORCH_CHECK(has(b1) && b1.numel() == Cs && has(b2) && b2.numel() == C, "se_gate: b1 [Cs], b2 [C]");
+  const c10::OptionalDeviceGuard guard(device_of(pooled));
+  Tensor h = torch::empty({N, Cs}, pooled.options());
+  Tensor gate = torch::empty({N, C}, pooled.options());
+  mpa::se_gate(pooled.data_ptr<float>(), bp(w1), fopt(b1), bp(w2), fopt(b2), (int)N, (int)C, (int)Cs,
+               h.data_ptr<float>(), gate.data_ptr<float>(), cur_stream());
+  return {h, gate};
+}
+
+Tensor act_gate_fwd(Tensor z, Tensor aff, int64_t act, Tensor gate) {
+  const mpa::SeGeom g = se_geom("act_gate_fwd", z, aff, act);
+  const float* gp = se_vec("act_gate_fwd", "gate", gate, g.N, g.C);
+  const c10::OptionalDeviceGuard guard(device_of(z));
+  Tensor u = torch::empty_like(z);
+  mpa::act_gate_fwd(bp(z), aff.data_ptr<float>(), (int)act, gp, g, bpm(u), cur_stream());
+  return u;
+}
+
+Tensor act_gate_bwd_pool(Tensor du, Tensor z, Tensor aff, int64_t act) {
+  const mpa::SeGeom g = se_geom("act_gate_bwd_pool", z, aff, act);
+  se_same("act_gate_bwd_pool", du, z);
+  const c10::OptionalDeviceGuard guard(device_of(z));
+  Tensor dgate = empty_like_shape(z, {g.N, g.C}, torch::kFloat32);
+  Tensor ws;
+  float* wsp = alloc_ws(ws, z, mpa::se_ws_floats(g, g.C));
+  mpa::act_gate_bwd_pool(bp(du), bp(z), aff.data_ptr<float>(), (int)act, g,
+                         dgate.data_ptr<float>(), wsp, cur_stream());
+  return dgate;
+}
+
+std::vector<Tensor> se_gate_bwd(Tensor dgate, Tensor h, Tensor gate, Tensor w1, Tensor w2,
+                                double inv_hw) {
+  CHECK_CUDA(dgate);
+  CHECK_F32(dgate);
+  CHECK_CONTIG(dgate);
+  TORCH_CHECK(dgate.dim() == 2 && h.dim() == 2 && w1.dim() >= 2 && w2.dim() >= 2,
+              "se_gate_bwd: dgate [N, C], h [N, Cs]");
+  const int64_t N = dgate.size(0), C = dgate.size(1), Cs = h.size(1);
+  se_fc_check("se_gate_bwd", w1, w2, N, C, Cs);
+  TORCH_CHECK(has(h) && h.numel() == N * Cs && has(gate) && gate.numel() == N * C,
+              "se_gate_bwd: h [N, Cs], gate [N, C]");
+  const c10::OptionalDeviceGuard guard(device_of(dgate));
+  Tensor dpre2 = torch::empty({N, C}, dgate.options());
+  Tensor dpre1 = torch::empty({N, Cs}, dgate.options());
+  Tensor dpool = torch::empty({N, C}, dgate.options());
+  mpa::se_gate_bwd(dgate.data_ptr<float>(), fopt(h), fopt(gate), bp(w1), bp(w2), (float)inv_hw,
+                   (int)N, (int)C, (int)Cs, dpre2.data_ptr<float>(), dpre1.data_ptr<float>(),
+                   dpool.data_ptr<float>(), cur_stream());
+  return {dpre2, dpre1, dpool};
+}
+
+void se_fc_wgrad(Tensor dpre, Tensor inp, Tensor dw, Tensor db, bool overwrite) {
+  CHECK_CUDA(dw);
+  CHECK_F32(dw);
+  CHECK_CONTIG(dw);
+  TORCH_CHECK(dpre.dim() == 2 && inp.dim() == 2 && dpre.size(0) == inp.size(0) && has(dpre) &&
+                  has(inp),
+              "se_fc_wgrad: dpre [N, O], inp [N, I]");
+  const int64_t N = dpre.size(0), O = dpre.size(1), I = inp.size(1);
+  TORCH_CHECK(dw.numel() == O * I && dw.size(0) == O && O * I + O < ((int64_t)1 << 31),
+              "se_fc_wgrad: dw [O, I]");
+  if (has(db)) TORCH_CHECK(db.numel() == O, "se_fc_wgrad: db [O]");
+  const c10::OptionalDeviceGuard guard(device_of(dpre));
+  mpa::se_fc_wgrad(fopt(dpre), fopt(inp), (int)N, (int)O, (int)I, dw.data_ptr<float>(),
+                   fopt_mut(db), overwrite, cur_stream());
+}
+
+Tensor act_gate_bwd_sums(Tensor du, Tensor z, Tensor aff, int64_t act, Tensor gate, Tensor dpool,
+                         Tensor mean, Tensor rstd) {
+  const char* op = "act_gate_bwd_sums";
+  const mpa::SeGeom g = se_geom(op, z, aff, act);
+  se_same(op, du, z);
+  TORCH_CHECK(has(mean) == has(rstd), op, ": mean and rstd come together");
+  const float* gp = se_vec(op, "gate", gate, g.N, g.C);
+  const float* dp = se_vec(op, "dpool", dpool, g.N, g.C);
+  const float* mp = se_vec(op, "mean", mean, 1, g.C);
+  const float* rp = se_vec(op, "rstd", rstd, 1, g.C);
+  const c10::OptionalDeviceGuard guard(device_of(z));
+  Tensor sums = empty_like_shape(z, {2, g.C}, torch::kFloat32);
+  Tensor ws;
+  float* wsp = alloc_ws(ws, z, mpa::se_ws_floats(g, 2 * g.C));
+  mpa::act_gate_bwd_sums(bp(du), bp(z), aff.data_ptr<float>(), (int)act, gp, dp, mp, rp, g,
+                         sums.data_ptr<float>(), wsp, cur_stream());
+  return sums;
+}
+
+Tensor act_gate_bwd_dx(Tensor du, Tensor z, Tensor aff, int64_t act, Tensor gate, Tensor dpool,
+                       Tensor mean, Tensor rstd, Tensor gamma, Tensor sums) {
+  const char* op = "act_gate_bwd_dx";
+  const mpa::SeGeom g = se_geom(op, z, aff, act);
+  se_same(op, du, z);
+  TORCH_CHECK(has(mean) == has(rstd), op, ": mean and rstd come together");
+  const float* gp = se_vec(op, "gate", gate, g.N, g.C);
+  const float* dp = se_vec(op, "dpool", dpool, g.N, g.C);
+  const float* mp = se_vec(op, "mean", mean, 1, g.C);
+  const float* rp = se_vec(op, "rstd", rstd, 1, g.C);
+  const float* gm = se_vec(op, "gamma", gamma, 1, g.C);
+  const float* sp = se_vec(op, "sums", sums, 2, g.C);
+  TORCH_CHECK(!mp || sp, op, ": sums [2, C] needed with mean / rstd");
+  const c10::OptionalDeviceGuard guard(device_of(z));
+  Tensor dz = torch::empty_like(z);
+  mpa::act_gate_bwd_dx(bp(du), bp(z), aff.data_ptr<float>(), (int)act, gp, dp, mp, rp, gm, sp, g,
+                       bpm(dz), cur_stream());
+  return dz;
+}
+
 Tensor act_bwd(Tensor dy, Tensor y, Tensor dbias) {
   CHECK_ACT(dy);
   const int C = dy.size(-1);
@@ -2097,6 +2265,24 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("sh"), py::arg("sw"), py::arg("ph"), py::arg("pw"), py::arg("accum") = py::none());
   m.def("dwconv_wgrad", &dwconv_wgrad, py::arg("dy"), py::arg("x"), py::arg("dw"), py::arg("sh"),
         py::arg("sw"), py::arg("ph"), py::arg("pw"), py::arg("overwrite") = false);
+  m.def("act_pool", &act_pool, py::arg("z"), py::arg("aff"), py::arg("act"),
+        "[N, C] mean over H x W of act(aff[0] z + aff[1]) (act 0 identity, 1 ReLU, 2 hardswish)");
+  m.def("se_gate", &se_gate, py::arg("pooled"), py::arg("w1"), py::arg("b1"), py::arg("w2"),
+        py::arg("b2"), "(h, gate) = (relu(W1 s + b1), hardsigmoid(W2 h + b2)) per image");
+  m.def("act_gate_fwd", &act_gate_fwd, py::arg("z"), py::arg("aff"), py::arg("act"),
+        py::arg("gate"), "bf16(act(t) gate[n, c]); empty gate: ones");
+  m.def("act_gate_bwd_pool", &act_gate_bwd_pool, py::arg("du"), py::arg("z"), py::arg("aff"),
+        py::arg("act"), "dgate [N, C] = sum over H x W of du act(t)");
+  m.def("se_gate_bwd", &se_gate_bwd, py::arg("dgate"), py::arg("h"), py::arg("gate"), py::arg("w1"),
+        py::arg("w2"), py::arg("inv_hw"), "(dpre2, dpre1, dpool) of the SE gate");
+  m.def("se_fc_wgrad", &se_fc_wgrad, py::arg("dpre"), py::arg("inp"), py::arg("dw"), py::arg("db"),
+        py::arg("overwrite") = false, "dw (+)= dpre^T inp, db (+)= column sums of dpre");
+  m.def("act_gate_bwd_sums", &act_gate_bwd_sums, py::arg("du"), py::arg("z"), py::arg("aff"),
+        py::arg("act"), py::arg("gate"), py::arg("dpool"), py::arg("mean"), py::arg("rstd"),
+        "[2, C] = [sum g | sum g xhat], g = (du gate + dpool) act'(t)");
+  m.def("act_gate_bwd_dx", &act_gate_bwd_dx, py::arg("du"), py::arg("z"), py::arg("aff"),
+        py::arg("act"), py::arg("gate"), py::arg("dpool"), py::arg("mean"), py::arg("rstd"),
+        py::arg("gamma"), py::arg("sums"), "the BN input gradient with g recomputed (or bf16(g))");
   m.def("conv_bnred_ok", &conv_bnred_ok);
   m.def("conv_dgrad_bnred_gacc", &conv_dgrad_bnred_gacc);
   m.def("conv_dgrad_res", &conv_dgrad_res);

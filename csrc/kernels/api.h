@@ -9,6 +9,7 @@
 
 #include "igemm_args.h"
 #include "dw_plan.h"
+#include "se_plan.h"
 
 namespace mpa {
 
@@ -120,6 +121,43 @@ void dwconv_dgrad(const bf16_raw* dy, const bf16_raw* w, const DwGeom& g, bf16_r
 int64_t dwconv_wgrad_ws_floats(const DwGeom& g);
 void dwconv_wgrad(const bf16_raw* dy, const bf16_raw* x, const DwGeom& g, float* dw,
                   bool overwrite, float* ws, hipStream_t s);
+
+// se.hip: squeeze-excite and activation-gate kernels, planned by se_plan.h.  z / du / u / dz
+// [N][HW][C] bf16, C % 8 == 0 (se_geom_error(g) == nullptr); t = aff[c] z + aff[C + c] in fp32;
+// act 0 identity, 1 ReLU, 2 hardswish.  No float atomics in any mode.  ws of the reducing
+// kernels: se_ws_floats(g, C) floats (the pools), se_ws_floats(g, 2 C) (the BN sums).
+// pooled [N][C] = mean over HW of act(t)
+void act_pool(const bf16_raw* z, const float* aff, int act, const SeGeom& g, float* pooled,
+              float* ws, hipStream_t s);
+// h [N][Cs] = relu(W1 pooled + b1), gate [N][C] = hardsigmoid(W2 h + b2); w1 [Cs][C], w2 [C][Cs]
+// bf16 (se_gate_error(N, C, Cs) == nullptr)
+void se_gate(const float* pooled, const bf16_raw* w1, const float* b1, const bf16_raw* w2,
+             const float* b2, int N, int C, int Cs, float* h, float* gate, hipStream_t s);
+// u = bf16(act(t) gate[n][c]); gate null: ones
+void act_gate_fwd(const bf16_raw* z, const float* aff, int act, const float* gate,
+                  const SeGeom& g, bf16_raw* u, hipStream_t s);
+// dgate [N][C] = sum over HW of du act(t)
+void act_gate_bwd_pool(const bf16_raw* du, const bf16_raw* z, const float* aff, int act,
+                       const SeGeom& g, float* dgate, float* ws, hipStream_t s);
+// dpre2 [N][C] = dgate / 6 where 0 < gate < 1; dpre1 [N][Cs] = W2^T dpre2 where h > 0;
+// dpool [N][C] = W1^T dpre1 inv_hw
+void se_gate_bwd(const float* dgate, const float* h, const float* gate, const bf16_raw* w1,
+                 const bf16_raw* w2, float inv_hw, int N, int C, int Cs, float* dpre2,
+                 float* dpre1, float* dpool, hipStream_t s);
+// dw [O][I] (+)= sum_n dpre[n][o] inp[n][i], db [O] (optional) (+)= sum_n dpre[n][o], in image
+// order
+void se_fc_wgrad(const float* dpre, const float* inp, int N, int O, int I, float* dw, float* db,
+                 bool overwrite, hipStream_t s);
+// g = (du gate + dpool) act'(t), xh = (z - mean) rstd: sums [2][C] = [sum g | sum g xh]
+// (gate, dpool optional; mean / rstd null: xh = 0)
+void act_gate_bwd_sums(const bf16_raw* du, const bf16_raw* z, const float* aff, int act,
+                       const float* gate, const float* dpool, const float* mean,
+                       const float* rstd, const SeGeom& g, float* sums, float* ws, hipStream_t s);
+// dz = bf16(gamma rstd (g - sum g / M - xh sum g xh / M)); mean / rstd null: dz = bf16(g)
+void act_gate_bwd_dx(const bf16_raw* du, const bf16_raw* z, const float* aff, int act,
+                     const float* gate, const float* dpool, const float* mean, const float* rstd,
+                     const float* gamma, const float* sums, const SeGeom& g, bf16_raw* dz,
+                     hipStream_t s);
 
 // bn.hip  (x/y/res/dy/dx: [M][C] bf16 rows; per-channel fp32 vectors)
 // ws: float workspace of bn_ws_floats(M, C) elements (per-block partial-sum slab)

@@ -29,6 +29,7 @@ from .squeezenet import squeezenet1_0, SqueezeNet
 from .densenet import densenet121, DenseNet
 from .inception import inception_v3, Inception3, InceptionOutputs
 from .mnasnet import mnasnet1_0, MNASNet
+from .mobilenetv3 import mobilenet_v3_large, MobileNetV3
 
 ARCH = {
     "resnet18": ("resnet18", resnet18, 224),
@@ -45,6 +46,11 @@ ARCH = {
 # size) entries; ``initialize_model`` looks a name up in ARCH, then here.
 EXTRA_ARCH = {
     "mnasnet": ("mnasnet1_0", mnasnet1_0, 224),
+}
+
+# Architectures on the squeeze-excite / hardswish kernels (se.hip), looked up after EXTRA_ARCH.
+SE_ARCH = {
+    "mobilenet_v3": ("mobilenet_v3_large", mobilenet_v3_large, 224),
 }
 
 
@@ -67,9 +73,10 @@ def _maybe_pretrained(model: nn.Module, arch: str) -> None:
 
 def initialize_model(model_name: str, num_classes: int, feature_extract: bool,
                      use_pretrained: bool = False) -> Tuple[nn.Module, int]:
-    if model_name not in ARCH and model_name not in EXTRA_ARCH:
+    entry = ARCH.get(model_name) or EXTRA_ARCH.get(model_name) or SE_ARCH.get(model_name)
+    if entry is None:
         raise ValueError("Invalid model name {!r}".format(model_name))
-    arch, ctor, input_size = ARCH.get(model_name) or EXTRA_ARCH[model_name]
+    arch, ctor, input_size = entry
     model = ctor(1000)
     if use_pretrained:
         _maybe_pretrained(model, arch)
@@ -87,6 +94,8 @@ def initialize_model(model_name: str, num_classes: int, feature_extract: bool,
         model.fc = Linear(model.fc.in_features, num_classes)
     elif model_name == "mnasnet":
         model.classifier[1] = Linear(model.classifier[1].in_features, num_classes)
+    elif model_name == "mobilenet_v3":
+        model.classifier[3] = Linear(model.classifier[3].in_features, num_classes)
     return model, input_size
 
 
@@ -109,8 +118,8 @@ def head_parameters(model: nn.Module):
             yield from m.parameters()
 
 
-__all__ = ["initialize_model", "set_parameter_requires_grad", "ARCH", "EXTRA_ARCH",
-           "InceptionOutputs", "mnasnet1_0",
+__all__ = ["initialize_model", "set_parameter_requires_grad", "ARCH", "EXTRA_ARCH", "SE_ARCH",
+           "InceptionOutputs", "mnasnet1_0", "mobilenet_v3_large",
            "input_spec",
            "resnet18", "resnet34", "vgg11_bn", "vgg16", "alexnet", "squeezenet1_0",
            "densenet121", "inception_v3"]

@@ -398,6 +398,32 @@ class _ReLUFn(torch.autograd.Function):
         return Fn.K(dy).act_bwd(dy.contiguous(), y, Fn._empty(dy))
 
 
+class Hardswish(nn.Module):
+    """x * relu6(x + 3) / 6.  Behind a BatchNorm the models fuse it into ``Fn.bn_act_gate``; this
+    module is the stand-alone form (MobileNetV3's classifier)."""
+
+    def __init__(self, inplace: bool = False):
+        super().__init__()
+
+    def forward(self, x):
+        return Fn.hardswish(x)
+
+
+class SqueezeExcitation(nn.Module):
+    """torchvision's SqueezeExcitation: ``fc1`` / ``fc2`` are 1x1 convs with bias (OIHW in the
+    state_dict), ReLU after the first and hardsigmoid after the second.  It has no forward of
+    its own: the gate scales the activation its BatchNorm feeds, so the layer is passed to
+    ``Fn.bn_act_gate`` / ``Fn.dwconv_bn_act_gate`` as ``se``."""
+
+    def __init__(self, channels: int, squeeze: int):
+        super().__init__()
+        self.fc1 = Conv2d(channels, squeeze, 1)
+        self.fc2 = Conv2d(squeeze, channels, 1)
+
+    def forward(self, x):
+        raise RuntimeError("SqueezeExcitation is applied by Fn.bn_act_gate(z, bn, act, se=layer)")
+
+
 class MaxPool2d(nn.Module):
     def __init__(self, kernel_size, stride=None, padding=0, ceil_mode=False):
         super().__init__()

@@ -994,6 +994,146 @@ def dwconv_bn_act(x, conv, bn, relu: bool = True):
     return bn_act(dwconv(x, conv), bn, relu=relu)
 
 
+# ================================================== BN -> activation -> squeeze-excite gate
+ACT_NONE, ACT_RELU, ACT_HARDSWISH = 0, 1, 2
+
+
+def _se_params(se):
+    if se is None:
+        return None, None, None, None
+    return se.fc1.weight, se.fc1.bias, se.fc2.weight, se.fc2.bias
+
+
+class _BNActGate(torch.autograd.Function):
+    """u = act(bn(z)) * gate, train mode, on the se.hip kernels: bn_stats_affine, then (with an
+    SE layer) act_pool -> se_gate, then act_gate_fwd.  act(bn(z)) is never stored: the backward
+    recomputes it from z.  Saved: z and per-channel / per-(image, channel) vectors."""
+
+    @staticmethod
+    def forward(ctx, z, gamma, beta, bn, act, stats, w1, b1, w2, b2):
+        k = K(z)
+        if stats is None:
+            stats = k.bn_stats(z, bn.running_mean)
+        mean, rstd, aff = k.bn_stats_affine(z, stats, gamma, beta, bn.running_mean,
+                                            bn.running_var, bn.momentum_value(), bn.eps,
+                                            bn.num_batches_tracked)
+        pooled = h = gate = None
+        if w1 is not None:
+            pooled = k.act_pool(z, aff, act)
+            h, gate = k.se_gate(pooled, weight_of(w1), b1, weight_of(w2), b2)
+        ctx.act = act
+        ctx.params = (gamma, beta, w1, b1, w2, b2)
+        ctx.save_for_backward(z, mean, rstd, aff, pooled, h, gate)
+        return k.act_gate_fwd(z, aff, act, _or_empty(gate, z))
+
+    @staticmethod
+    def backward(ctx, du):
+        z, mean, rstd, aff, pooled, h, gate = ctx.saved_tensors
+        gamma, beta, w1, b1, w2, b2 = ctx.params
+        k = K(du)
+        du = du.contiguous()
+        act = ctx.act
+        dpool = None
+        if gate is not None:
+            dgate = k.act_gate_bwd_pool(du, z, aff, act)
+            dpre2, dpre1, dpool = k.se_gate_bwd(dgate, h, gate, weight_of(w1), weight_of(w2),
+                                                1.0 / (z.shape[1] * z.shape[2]))
+
+            def wgrad():
+                for w, b, dpre, inp in ((w2, b2, dpre2, h), (w1, b1, dpre1, pooled)):
+                    if w.requires_grad:
+                        bs = _sink(b, du)
+                        fresh = _fresh(w)  # (both flags are consumed)
+                        fresh = (_fresh(b) if bs.numel() else True) and fresh
+                        k.se_fc_wgrad(dpre, inp, grad_sink(w), bs, overwrite=fresh)
+                        _done(w, b)
+            _run_wgrad(wgrad, dpre2, h, dpre1, pooled)
+        sums = k.act_gate_bwd_sums(du, z, aff, act, _or_empty(gate, du), _or_empty(dpool, du),
+                                   mean, rstd)
+        for p, row in ((gamma, 1), (beta, 0)):  # dgamma = sum g xhat, dbeta = sum g
+            sink = _sink(p, du)
+            if sink.numel():
+                k.add_f32_(sink, sums[row])
+        _done(gamma, beta)
+        dz = None
+        if ctx.needs_input_grad[0]:
+            dz = k.act_gate_bwd_dx(du, z, aff, act, _or_empty(gate, du), _or_empty(dpool, du),
+                                   mean, rstd, gamma, sums)
+        return _grads(_BNActGate, dz)
+
+
+def _eval_affine(bn):
+    """An eval-mode BN as the [2, C] affine the se.hip kernels apply."""
+    sc = bn.weight.float() * torch.rsqrt(bn.running_var + bn.eps)
+    return torch.stack([sc, bn.bias.float() - bn.running_mean * sc]).contiguous()
+
+
+def bn_act_gate(z, bn, act: int, se=None, stats: Optional[torch.Tensor] = None):
+    """act(bn(z)) * gate with act in (ACT_NONE, ACT_RELU, ACT_HARDSWISH); ``se``: a
+    SqueezeExcitation layer, whose per-(image, channel) gate is hardsigmoid(fc2(relu(fc1(mean
+    over H x W of act(bn(z)))))), or None (no gate); ``stats`` (train mode): z's [mean | var]
+    from its producer's epilogue."""
+    w1, b1, w2, b2 = _se_params(se)
+    if bn.training:
+        return _BNActGate.apply(z, bn.weight, bn.bias, bn, act, stats, w1, b1, w2, b2)
+    k = K(z)
+    aff = _eval_affine(bn)
+    gate = _empty(z)
+    if se is not None:
+        _h, gate = k.se_gate(k.act_pool(z, aff, act), weight_of(w1), b1, weight_of(w2), b2)
+    return k.act_gate_fwd(z, aff, act, gate)
+
+
+def dwconv_bn_act_gate(x, conv, bn, act: int, se=None):
+    """bn_act_gate(dwconv(x)): train mode takes the BN statistics from the conv's epilogue.
+    ReLU without a gate is ``dwconv_bn_act``."""
+    if act == ACT_RELU and se is None:
+        return dwconv_bn_act(x, conv, bn, relu=True)
+    if bn.training:
+        stats = torch.empty(2, conv.out_channels, device=x.device, dtype=torch.float32)
+        z = dwconv(x, conv, stats, None if _NO_SHIFT else bn.running_mean)
+        return bn_act_gate(z, bn, act, se, stats)
+    return bn_act_gate(dwconv(x, conv), bn, act, se)
+
+
+def conv_bn_act_gate(x, conv, bn, act: int):
+    """act(bn(conv(x))) for a bias-free conv; ReLU and identity are ``conv_bn_act``."""
+    if act != ACT_HARDSWISH:
+        return conv_bn_act(x, conv, bn, relu=act == ACT_RELU)
+    if bn.training:
+        stats = torch.empty(2, conv.cout_store, device=x.device, dtype=torch.float32)
+        z = conv_act(x, conv, False, stats=stats, shift=None if _NO_SHIFT else bn.running_mean)
+        return bn_act_gate(z, bn, act, None, stats)
+    return bn_act_gate(conv_act(x, conv, False), bn, act)
+
+
+class _Hardswish(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, aff):
+        ctx.save_for_backward(x, aff)
+        return K(x).act_gate_fwd(x, aff, ACT_HARDSWISH, _empty(x))
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, aff = ctx.saved_tensors
+        e = _empty(dy)
+        return K(dy).act_gate_bwd_dx(dy.contiguous(), x, aff, ACT_HARDSWISH, e, e, e, e, e, e), None
+
+
+def hardswish(x):
+    """x * relu6(x + 3) / 6 (act_gate_fwd with the unit affine [1 | 0], no gate)."""
+    C = x.shape[-1]
+    key = ("hswish", C, x.device)
+    aff = _UNIT.get(key)
+    if aff is None:
+        aff = _UNIT[key] = torch.stack([torch.ones(C, device=x.device),
+                                        torch.zeros(C, device=x.device)])
+    x = x.contiguous()
+    if torch.is_grad_enabled() and x.requires_grad:
+        return _Hardswish.apply(x, aff)
+    return K(x).act_gate_fwd(x, aff, ACT_HARDSWISH, _empty(x))
+
+
 # =========================================================================== standalone BN
 class _BNAct(torch.autograd.Function):
     @staticmethod

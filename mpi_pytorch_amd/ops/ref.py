@@ -171,6 +171,105 @@ def dwconv_wgrad(dy, x, dw, sh, sw, ph, pw, overwrite=False):
         dw.add_(gw.permute(0, 2, 3, 1))
 
 
+# ------------------------------------------------------- squeeze-excite / activation gate
+def _se_t(z, aff):
+    """t = aff[0] z + aff[1] as one rounding of the exact value (the kernels' fused
+    multiply-add), [N, HW, C] fp32; a 2-D z is one image of its rows."""
+    C = z.shape[-1]
+    z3 = z.reshape(z.shape[0] if z.dim() == 4 else 1, -1, C)
+    return torch.addcmul(aff[1].double(), z3.double(), aff[0].double()).float()
+
+
+def _se_act(t, act):
+    if act == 1:
+        return torch.relu(t)
+    if act == 2:
+        return t * torch.clamp(t + 3, 0, 6) / 6
+    return t
+
+
+def _se_der(t, act):
+    if act == 1:
+        return (t > 0).float()
+    if act == 2:  # torch's hardswish_backward
+        return torch.where(t <= -3, torch.zeros_like(t),
+                           torch.where(t >= 3, torch.ones_like(t), t / 3 + 0.5))
+    return torch.ones_like(t)
+
+
+def _se_g(du, z, aff, act, gate, dpool):
+    t = _se_t(z, aff)
+    g = _f(du).reshape(t.shape)
+    if _opt(gate) is not None:
+        g = g * gate.reshape(t.shape[0], 1, -1)
+    if _opt(dpool) is not None:
+        g = g + dpool.reshape(t.shape[0], 1, -1)
+    return g * _se_der(t, act)
+
+
+def act_pool(z, aff, act):
+    return _se_act(_se_t(z, aff), act).mean(1)
+
+
+def se_gate(pooled, w1, b1, w2, b2):
+    Cs, C = w1.shape[0], pooled.shape[1]
+    h = torch.relu(pooled @ _f(w1).reshape(Cs, C).t() + b1)
+    gate = torch.clamp(h @ _f(w2).reshape(C, Cs).t() + b2 + 3, 0, 6) / 6
+    return h, gate
+
+
+def act_gate_fwd(z, aff, act, gate):
+    u = _se_act(_se_t(z, aff), act)
+    if _opt(gate) is not None:
+        u = u * gate.reshape(u.shape[0], 1, -1)
+    return u.reshape(z.shape).to(z.dtype)
+
+
+def act_gate_bwd_pool(du, z, aff, act):
+    t = _se_t(z, aff)
+    return (_f(du).reshape(t.shape) * _se_act(t, act)).sum(1)
+
+
+def se_gate_bwd(dgate, h, gate, w1, w2, inv_hw):
+    Cs, C = h.shape[1], dgate.shape[1]
+    dpre2 = torch.where((gate > 0) & (gate < 1), dgate / 6, torch.zeros_like(dgate))
+    dpre1 = (dpre2 @ _f(w2).reshape(C, Cs)) * (h > 0)
+    return dpre2, dpre1, (dpre1 @ _f(w1).reshape(Cs, C)) * inv_hw
+
+
+def se_fc_wgrad(dpre, inp, dw, db, overwrite=False):
+    gw = (dpre.t() @ inp).reshape(dw.shape)
+    if overwrite:
+        dw.copy_(gw)
+    else:
+        dw.add_(gw)
+    if _opt(db) is not None:
+        if overwrite:
+            db.copy_(dpre.sum(0))
+        else:
+            db.add_(dpre.sum(0))
+
+
+def act_gate_bwd_sums(du, z, aff, act, gate, dpool, mean, rstd):
+    g = _se_g(du, z, aff, act, gate, dpool)
+    C = g.shape[-1]
+    sg = g.reshape(-1, C).sum(0)
+    if _opt(mean) is None:
+        return torch.stack([sg, torch.zeros_like(sg)])
+    xh = (_f(z).reshape(g.shape) - mean) * rstd
+    return torch.stack([sg, (g * xh).reshape(-1, C).sum(0)])
+
+
+def act_gate_bwd_dx(du, z, aff, act, gate, dpool, mean, rstd, gamma, sums):
+    g = _se_g(du, z, aff, act, gate, dpool)
+    if _opt(mean) is not None:
+        M = g.shape[0] * g.shape[1]
+        xh = (_f(z).reshape(g.shape) - mean) * rstd
+        k1 = rstd if _opt(gamma) is None else gamma.float() * rstd
+        g = k1 * (g - sums[0] / M - xh * (sums[1] / M))
+    return g.reshape(z.shape).to(z.dtype)
+
+
 def act_bwd(dy, y, dbias):
     """g = dy * (y > 0) if y given else dy; dbias += sum_rows(g)."""
     g = dy if _opt(y) is None else (_f(dy) * (_f(y) > 0)).to(dy.dtype)
