@@ -749,6 +749,80 @@ Tensor act_gate_bwd_dx(Tensor du, Tensor z, Tensor aff, int64_t act, Tensor gate
   return dz;
 }
 
+// ------------------------------------------------------------------------ grouped conv
+// x [N, H, W, C] bf16, w [C, 3, 3, Cg] bf16 (layers.Conv2d groups = C / Cg); 3x3, padding 1, one
+// stride in {1, 2}, Cg in {4, 8, 16, 32}, C % 16 == 0: anything else is refused
+static mpa::GcGeom gc_geom(const char* op, const Tensor& w, int64_t N, int64_t H, int64_t W,
+                           int64_t C, int64_t sh, int64_t sw, int64_t ph, int64_t pw) {
+  TORCH_CHECK(w.dim() == 4 && w.size(1) == w.size(2) && w.size(3) > 0 && C % w.size(3) == 0, op,
+              ": w must be [C, k, k, Cg] with Cg dividing the channels");
+  TORCH_CHECK(sh == sw && ph == 1 && pw == 1, op,
+              ": one stride for both directions and padding 1, got stride (", sh, ", ", sw,
+              "), padding (", ph, ", ", pw, ")");
+  TORCH_CHECK(N > 0 && N < (1 << 24) && H < (1 << 24) && W < (1 << 24) && C < (1 << 24), op,
+              ": extent");
+  const mpa::GcGeom g{(int)N, (int)H, (int)W, (int)C, (int)w.size(0), (int)(C / w.size(3)),
+                      (int)w.size(1), (int)sh};
+  const char* err = mpa::gconv_geom_error(g);
+  TORCH_CHECK(!err, op, ": ", err);
+  return g;
+}
+
+Tensor gconv_fwd(Tensor x, Tensor w, int64_t sh, int64_t sw, int64_t ph, int64_t pw, Tensor stats,
+                 Tensor shift) {
+  CHECK_ACT(x);
+  CHECK_ACT(w);
+  TORCH_CHECK(x.dim() == 4 && aligned16(x) && aligned16(w),
+              "gconv_fwd: x NHWC, x and w 16-byte aligned");
+  const mpa::GcGeom g =
+      gc_geom("gconv_fwd", w, x.size(0), x.size(1), x.size(2), x.size(3), sh, sw, ph, pw);
+  const int P = mpa::gc_out(g.H, g.s), Q = mpa::gc_out(g.W, g.s);
+  if (has(stats)) TORCH_CHECK(stats.numel() == 2 * g.C, "gconv_fwd: stats size");
+  if (has(shift)) TORCH_CHECK(shift.numel() == g.C, "gconv_fwd: shift size");
+  const c10::OptionalDeviceGuard guard(device_of(x));
+  Tensor z = empty_like_shape(x, {g.N, P, Q, g.C}, torch::kBFloat16);
+  float* st = fopt_mut(stats);
+  Tensor ws;
+  float* wsp = st ? alloc_ws(ws, x, mpa::gconv_fwd_ws_floats(g)) : nullptr;
+  mpa::gconv_fwd(bp(x), bp(w), g, bpm(z), st, st ? fopt(shift) : nullptr, wsp, cur_stream());
+  return z;
+}
+
+Tensor gconv_dgrad(Tensor dy, Tensor w, int64_t H, int64_t W, int64_t sh, int64_t sw, int64_t ph,
+                   int64_t pw) {
+  CHECK_ACT(dy);
+  CHECK_ACT(w);
+  TORCH_CHECK(dy.dim() == 4 && aligned16(dy) && aligned16(w),
+              "gconv_dgrad: dy NHWC, dy and w 16-byte aligned");
+  const mpa::GcGeom g = gc_geom("gconv_dgrad", w, dy.size(0), H, W, dy.size(3), sh, sw, ph, pw);
+  TORCH_CHECK(dy.size(1) == mpa::gc_out(g.H, g.s) && dy.size(2) == mpa::gc_out(g.W, g.s),
+              "gconv_dgrad: dy is not the conv output of an H x W input");
+  const c10::OptionalDeviceGuard guard(device_of(dy));
+  Tensor dx = empty_like_shape(dy, {g.N, H, W, g.C}, torch::kBFloat16);
+  mpa::gconv_dgrad(bp(dy), bp(w), g, bpm(dx), cur_stream());
+  return dx;
+}
+
+void gconv_wgrad(Tensor dy, Tensor x, Tensor dw, int64_t sh, int64_t sw, int64_t ph, int64_t pw,
+                 bool overwrite) {
+  CHECK_ACT(dy);
+  CHECK_ACT(x);
+  CHECK_CUDA(dw);
+  CHECK_F32(dw);
+  CHECK_CONTIG(dw);
+  TORCH_CHECK(x.dim() == 4 && dy.dim() == 4 && dy.size(3) == x.size(3) &&
+                  dy.size(0) == x.size(0) && aligned16(x) && aligned16(dy),
+              "gconv_wgrad: x, dy NHWC (16-byte aligned) with the same channels and one batch");
+  const mpa::GcGeom g =
+      gc_geom("gconv_wgrad", dw, x.size(0), x.size(1), x.size(2), x.size(3), sh, sw, ph, pw);
+  TORCH_CHECK(dy.size(1) == mpa::gc_out(g.H, g.s) && dy.size(2) == mpa::gc_out(g.W, g.s),
+              "gconv_wgrad: dy is not the conv output of x");
+  const c10::OptionalDeviceGuard guard(device_of(dy));
+  Tensor ws;
+  float* wsp = alloc_ws(ws, dy, mpa::gconv_wgrad_ws_floats(g));
+  mpa::gconv_wgrad(bp(dy), bp(x), g, dw.data_ptr<float>(), overwrite, wsp, cur_stream());
+}
+
 Tensor act_bwd(Tensor dy, Tensor y, Tensor dbias) {
   CHECK_ACT(dy);
   const int C = dy.size(-1);
@@ -2283,6 +2357,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("act_gate_bwd_dx", &act_gate_bwd_dx, py::arg("du"), py::arg("z"), py::arg("aff"),
         py::arg("act"), py::arg("gate"), py::arg("dpool"), py::arg("mean"), py::arg("rstd"),
         py::arg("gamma"), py::arg("sums"), "the BN input gradient with g recomputed (or bf16(g))");
+  m.def("gconv_fwd", &gconv_fwd, py::arg("x"), py::arg("w"), py::arg("sh"), py::arg("sw"),
+        py::arg("ph"), py::arg("pw"), py::arg("stats"), py::arg("shift"),
+        "grouped 3x3 conv forward (+ BN statistics of its output)");
+  m.def("gconv_dgrad", &gconv_dgrad, py::arg("dy"), py::arg("w"), py::arg("H"), py::arg("W"),
+        py::arg("sh"), py::arg("sw"), py::arg("ph"), py::arg("pw"));
+  m.def("gconv_wgrad", &gconv_wgrad, py::arg("dy"), py::arg("x"), py::arg("dw"), py::arg("sh"),
+        py::arg("sw"), py::arg("ph"), py::arg("pw"), py::arg("overwrite") = false);
   m.def("conv_bnred_ok", &conv_bnred_ok);
   m.def("conv_dgrad_bnred_gacc", &conv_dgrad_bnred_gacc);
   m.def("conv_dgrad_res", &conv_dgrad_res);

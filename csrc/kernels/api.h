@@ -9,6 +9,7 @@
 
 #include "igemm_args.h"
 #include "dw_plan.h"
+#include "gconv_plan.h"
 #include "se_plan.h"
 
 namespace mpa {
@@ -158,6 +159,23 @@ void act_gate_bwd_dx(const bf16_raw* du, const bf16_raw* z, const float* aff, in
                      const float* gate, const float* dpool, const float* mean, const float* rstd,
                      const float* gamma, const float* sums, const SeGeom& g, bf16_raw* dz,
                      hipStream_t s);
+
+// conv_group.hip: grouped 3x3 conv on MFMA, NHWC bf16, cin == cout == C, C % 16 == 0,
+// C / groups in {4, 8, 16, 32}, padding 1, stride in {1, 2}, weight [C][3][3][Cg]
+// (gconv_geom_error(g) == nullptr); planned by gconv_plan.h.  No float atomics: every reduction
+// is partial rows into ws, then a fixed-order sum.
+// fwd: stats (optional) receives [mean | var] [2][C] of the stored z, sums shifted by shift
+// (optional); ws holds gconv_fwd_ws_floats(g) floats when stats is set
+int64_t gconv_fwd_ws_floats(const GcGeom& g);
+void gconv_fwd(const bf16_raw* x, const bf16_raw* w, const GcGeom& g, bf16_raw* z, float* stats,
+               const float* shift, float* ws, hipStream_t s);
+// dx [N][H][W][C] = dgrad(dy)
+void gconv_dgrad(const bf16_raw* dy, const bf16_raw* w, const GcGeom& g, bf16_raw* dx,
+                 hipStream_t s);
+// dw [C][3][3][Cg] fp32 (+)= weight gradient; ws holds gconv_wgrad_ws_floats(g) floats
+int64_t gconv_wgrad_ws_floats(const GcGeom& g);
+void gconv_wgrad(const bf16_raw* dy, const bf16_raw* x, const GcGeom& g, float* dw, bool overwrite,
+                 float* ws, hipStream_t s);
 
 // bn.hip  (x/y/res/dy/dx: [M][C] bf16 rows; per-channel fp32 vectors)
 // ws: float workspace of bn_ws_floats(M, C) elements (per-block partial-sum slab)

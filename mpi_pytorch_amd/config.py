@@ -21,7 +21,7 @@ from dataclasses import dataclass, field, fields
 from typing import Any, Dict, List, Optional
 
 MODEL_NAMES = ("resnet18", "resnet34", "alexnet", "vgg", "vgg16", "squeezenet",
-               "densenet", "inception", "mnasnet", "mobilenet_v3")
+               "densenet", "inception", "mnasnet", "mobilenet_v3", "resnext50")
 
 _ENV_PREFIX = "MPA_"
 

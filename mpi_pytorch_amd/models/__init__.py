@@ -23,7 +23,7 @@ import torch
 import torch.nn as nn
 
 from .layers import Conv2d, Linear
-from .resnet import resnet18, resnet34, ResNet
+from .resnet import resnet18, resnet34, resnext50_32x4d, ResNet
 from .vgg import vgg11_bn, vgg16, alexnet, VGG, AlexNet
 from .squeezenet import squeezenet1_0, SqueezeNet
 from .densenet import densenet121, DenseNet
@@ -53,6 +53,11 @@ SE_ARCH = {
     "mobilenet_v3": ("mobilenet_v3_large", mobilenet_v3_large, 224),
 }
 
+# Architectures on the grouped-conv kernels (conv_group.hip), looked up after SE_ARCH.
+GROUPED_ARCH = {
+    "resnext50": ("resnext50_32x4d", resnext50_32x4d, 224),
+}
+
 
 def set_parameter_requires_grad(model: nn.Module, feature_extracting: bool) -> None:
     if feature_extracting:
@@ -73,7 +78,8 @@ def _maybe_pretrained(model: nn.Module, arch: str) -> None:
 
 def initialize_model(model_name: str, num_classes: int, feature_extract: bool,
                      use_pretrained: bool = False) -> Tuple[nn.Module, int]:
-    entry = ARCH.get(model_name) or EXTRA_ARCH.get(model_name) or SE_ARCH.get(model_name)
+    entry = (ARCH.get(model_name) or EXTRA_ARCH.get(model_name) or SE_ARCH.get(model_name)
+             or GROUPED_ARCH.get(model_name))
     if entry is None:
         raise ValueError("Invalid model name {!r}".format(model_name))
     arch, ctor, input_size = entry
@@ -81,7 +87,7 @@ def initialize_model(model_name: str, num_classes: int, feature_extract: bool,
     if use_pretrained:
         _maybe_pretrained(model, arch)
     set_parameter_requires_grad(model, feature_extract)
-    if model_name in ("resnet18", "resnet34"):
+    if model_name in ("resnet18", "resnet34", "resnext50"):
         model.fc = Linear(model.fc.in_features, num_classes, bias=True)
     elif model_name in ("alexnet", "vgg", "vgg16"):
         model.classifier[6] = Linear(model.classifier[6].in_features, num_classes)
@@ -119,7 +125,8 @@ def head_parameters(model: nn.Module):
 
 
 __all__ = ["initialize_model", "set_parameter_requires_grad", "ARCH", "EXTRA_ARCH", "SE_ARCH",
-           "InceptionOutputs", "mnasnet1_0", "mobilenet_v3_large",
+           "GROUPED_ARCH", "InceptionOutputs", "mnasnet1_0", "mobilenet_v3_large",
+           "resnext50_32x4d",
            "input_spec",
            "resnet18", "resnet34", "vgg11_bn", "vgg16", "alexnet", "squeezenet1_0",
            "densenet121", "inception_v3"]

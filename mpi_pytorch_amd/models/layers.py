@@ -70,22 +70,31 @@ class Conv2d(nn.Module):
     def __init__(self, in_channels: int, out_channels: int, kernel_size, stride=1, padding=0,
                  bias: bool = True, pad_out: bool = False, groups: int = 1):
         super().__init__()
-        if groups != 1 and not (groups == in_channels == out_channels):
-            raise ValueError("Conv2d: groups must be 1 or in_channels == out_channels "
-                             "(depthwise), got groups={} for {} -> {} channels".format(
-                                 groups, in_channels, out_channels))
+        kh0, kw0 = _pair(kernel_size)
+        # grouped: the geometries the gconv kernels take (conv_group.hip): 3x3, padding 1, one
+        # stride in {1, 2}, in == out channels a multiple of 16, 4 / 8 / 16 / 32 per group
+        self.grouped = (groups != 1 and groups != in_channels and in_channels == out_channels
+                        and in_channels % 16 == 0 and in_channels % groups == 0
+                        and in_channels // groups in (4, 8, 16, 32) and (kh0, kw0) == (3, 3)
+                        and _pair(padding) == (1, 1) and _pair(stride) in ((1, 1), (2, 2)))
+        if groups != 1 and not self.grouped and not (groups == in_channels == out_channels):
+            raise ValueError("Conv2d: groups must be 1, in_channels == out_channels (depthwise) "
+                             "or a grouped 3x3 (padding 1, stride 1 or 2, equal channels % 16 == "
+                             "0, 4 / 8 / 16 / 32 per group), got groups={} for {} -> {} channels, "
+                             "kernel {}".format(groups, in_channels, out_channels, (kh0, kw0)))
         self.groups = groups
         # depthwise: weight stored [C, R, S, 1] (OIHW [C, 1, R, S]), run by the dwconv kernels
         # (Fn.dwconv); no channel padding, no pixel pairs, no transposed copy (the kernels
-        # transpose their channel chunk of the stored weight while staging it)
-        self.depthwise = groups != 1
+        # transpose their channel chunk of the stored weight while staging it).  grouped: weight
+        # stored [C, 3, 3, Cg] (OIHW [C, Cg, 3, 3]), run by the gconv kernels (Fn.gconv), which
+        # expand and transpose it while they build their MFMA fragments
+        self.depthwise = groups != 1 and not self.grouped
         self.cin_w = in_channels // groups  # the weight's input-channel extent
         self.in_channels = in_channels
-        kh0, kw0 = _pair(kernel_size)
         self.pair = (_PAIR_STEM and in_channels <= 4 and _pair(stride)[1] == 2 and kw0 >= 2)
         self.cin_store = 8 if in_channels < 8 else in_channels
-        if self.depthwise:
-            self.pair, self.cin_store = False, 1
+        if self.depthwise or self.grouped:
+            self.pair, self.cin_store = False, self.cin_w
         self.out_channels = out_channels
         # pad_out: store the output channels rounded up to a multiple of 32 (zero filters) -
         # for classifier convs (SqueezeNet's 512 -> 64,500 1x1 head) so their dgrad / wgrad
@@ -108,7 +117,7 @@ class Conv2d(nn.Module):
         self.weight._mpa_import = self._imp
         # (K, R*S, C) of the stored KRSC weight: the arena keeps a [C][R*S][K] copy for dgrad
         ks = self.sp if self.pair else kw
-        if not self.depthwise:
+        if not self.depthwise and not self.grouped:
             self.weight._mpa_tlayout = (self.cout_store, kh * ks, self.cin_store)
         if bias:
             fan_in = self.cin_w * kh * kw
@@ -185,6 +194,9 @@ class Conv2d(nn.Module):
         if self.depthwise:
             y = Fn.dwconv(x, self)
             return ReLU()(y) if relu else y
+        if self.grouped:
+            y = Fn.gconv(x, self)
+            return ReLU()(y) if relu else y
         return Fn.conv_act(x, self, relu=relu)
 
     def input_spec(self, hw) -> dict:
@@ -231,7 +243,7 @@ class Conv2d(nn.Module):
     def extra_repr(self):
         return "{}, {}, kernel_size={}, stride={}, padding={}, bias={}{}".format(
             self.in_channels, self.out_channels, self.kernel_size, self.stride, self.padding,
-            self.bias is not None, ", groups=%d" % self.groups if self.depthwise else "")
+            self.bias is not None, ", groups=%d" % self.groups if self.groups != 1 else "")
 
 
 class BatchNorm2d(nn.Module):

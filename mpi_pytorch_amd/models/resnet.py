@@ -1,4 +1,5 @@
-"""ResNet-18/34 (BasicBlock), NHWC, torchvision parameter names.
+"""ResNet-18/34 (BasicBlock) and ResNeXt-50 32x4d (Bottleneck), NHWC, torchvision parameter
+names.
 
 Reference: ``models.resnet18`` / ``models.resnet34`` with ``fc`` replaced by
 ``nn.Linear(512, num_classes)`` (``/root/reference/models.py:30-45``).  Each
@@ -61,13 +62,50 @@ class BasicBlock(nn.Module):
                               link_in=link, join_res=join_res, res_defer=dsd)
 
 
+class Bottleneck(nn.Module):
+    """torchvision's bottleneck: 1x1 -> grouped 3x3 (carries the stride) -> 1x1, expansion 4.
+    The 1x1 convs run on the rows GEMM (``conv_bn_act``), the grouped 3x3 on the gconv kernels
+    (``gconv_bn_act``); every BN takes its statistics from its conv's epilogue."""
+    expansion = 4
+
+    def __init__(self, inplanes: int, planes: int, stride: int = 1, downsample=None,
+                 groups: int = 1, width_per_group: int = 64):
+        super().__init__()
+        width = int(planes * (width_per_group / 64.0)) * groups
+        self.conv1 = Conv2d(inplanes, width, 1, bias=False)
+        self.bn1 = BatchNorm2d(width)
+        self.conv2 = Conv2d(width, width, 3, stride, 1, bias=False, groups=groups)
+        if not self.conv2.grouped:
+            raise ValueError("Bottleneck: conv2 must be a grouped 3x3 the gconv kernels take, got "
+                             "groups={} at width {}".format(groups, width))
+        self.bn2 = BatchNorm2d(width)
+        self.conv3 = Conv2d(width, planes * self.expansion, 1, bias=False)
+        self.bn3 = BatchNorm2d(planes * self.expansion)
+        self.relu = ReLU(inplace=True)
+        self.downsample = downsample
+        self.stride = stride
+
+    def forward(self, x):
+        out = Fn.conv_bn_act(x, self.conv1, self.bn1, relu=True)
+        out = Fn.gconv_bn_act(out, self.conv2, self.bn2, relu=True)
+        identity = x
+        if self.downsample is not None:
+            identity = Fn.conv_bn_act(x, self.downsample[0], self.downsample[1], relu=False)
+        return Fn.conv_bn_act(out, self.conv3, self.bn3, relu=True, residual=identity)
+
+
 class Downsample(nn.Sequential):
     pass
 
 
 class ResNet(nn.Module):
-    def __init__(self, layers, num_classes: int = 1000):
+    def __init__(self, layers, num_classes: int = 1000, block=BasicBlock, groups: int = 1,
+                 width_per_group: int = 64):
         super().__init__()
+        self.block = block
+        # (BasicBlock takes no group arguments: ResNet-18/34 are built exactly as before)
+        self.block_args = {} if block is BasicBlock else {"groups": groups,
+                                                          "width_per_group": width_per_group}
         self.inplanes = 64
         self.conv1 = Conv2d(3, 64, 7, 2, 3, bias=False)
         self.bn1 = BatchNorm2d(64)
@@ -78,20 +116,21 @@ class ResNet(nn.Module):
         self.layer3 = self._make_layer(256, layers[2], stride=2)
         self.layer4 = self._make_layer(512, layers[3], stride=2)
         self.avgpool = AdaptiveAvgPool2d((1, 1))
-        self.fc = Linear(512, num_classes)
+        self.fc = Linear(512 * block.expansion, num_classes)
         for m in self.modules():
             if isinstance(m, Conv2d):
                 m.init_(lambda w: nn.init.kaiming_normal_(w, mode="fan_out", nonlinearity="relu"))
 
     def _make_layer(self, planes: int, blocks: int, stride: int = 1):
         downsample = None
-        if stride != 1 or self.inplanes != planes:
-            downsample = Downsample(Conv2d(self.inplanes, planes, 1, stride, 0, bias=False),
-                                    BatchNorm2d(planes))
-        layers = [BasicBlock(self.inplanes, planes, stride, downsample)]
-        self.inplanes = planes
+        block, out = self.block, planes * self.block.expansion
+        if stride != 1 or self.inplanes != out:
+            downsample = Downsample(Conv2d(self.inplanes, out, 1, stride, 0, bias=False),
+                                    BatchNorm2d(out))
+        layers = [block(self.inplanes, planes, stride, downsample, **self.block_args)]
+        self.inplanes = out
         for _ in range(1, blocks):
-            layers.append(BasicBlock(self.inplanes, planes))
+            layers.append(block(self.inplanes, planes, **self.block_args))
         return nn.Sequential(*layers)
 
     def forward(self, x):
@@ -110,3 +149,7 @@ def resnet18(num_classes: int = 1000) -> ResNet:
 
 def resnet34(num_classes: int = 1000) -> ResNet:
     return ResNet([3, 4, 6, 3], num_classes)
+
+
+def resnext50_32x4d(num_classes: int = 1000) -> ResNet:
+    return ResNet([3, 4, 6, 3], num_classes, block=Bottleneck, groups=32, width_per_group=4)

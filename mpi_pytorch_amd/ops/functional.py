@@ -1134,6 +1134,59 @@ def hardswish(x):
     return K(x).act_gate_fwd(x, aff, ACT_HARDSWISH, _empty(x))
 
 
+# ========================================================================== grouped conv
+class _GConv(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, w, conv, stats=None, shift=None):
+        k = K(x)
+        sh, sw, ph, pw = conv.kgeom
+        z = k.gconv_fwd(x, weight_of(w), sh, sw, ph, pw, _or_empty(stats, x),
+                        _or_empty(shift, x))
+        ctx.conv, ctx.w = conv, w
+        ctx.in_hw = (x.shape[1], x.shape[2])
+        ctx.save_for_backward(x)
+        return z
+
+    @staticmethod
+    def backward(ctx, dz):
+        (x,) = ctx.saved_tensors
+        w, conv = ctx.w, ctx.conv
+        k = K(dz)
+        dz = dz.contiguous()
+        sh, sw, ph, pw = conv.kgeom
+        if w.requires_grad:
+            def wgrad():
+                k.gconv_wgrad(dz, x, w.grad, sh, sw, ph, pw, overwrite=_fresh(w))
+                _done(w)
+            _run_wgrad(wgrad, dz, x)
+        dx = None
+        if ctx.needs_input_grad[0]:
+            dx = k.gconv_dgrad(dz, weight_of(w), *ctx.in_hw, sh, sw, ph, pw)
+        return _grads(_GConv, dx)
+
+
+def gconv(x, conv, stats: Optional[torch.Tensor] = None, shift: Optional[torch.Tensor] = None):
+    """Grouped 3x3 conv (``conv.grouped``, no bias); ``stats`` ([2, C] fp32): receives the
+    output's per-channel [mean | var] from the kernel's epilogue (sums shifted by ``shift``) in
+    the format ``bn_act(stats=)`` takes."""
+    if not conv.grouped or conv.bias is not None:
+        raise ValueError("gconv: a bias-free grouped 3x3 Conv2d expected")
+    if torch.is_grad_enabled() and (conv.weight.requires_grad or x.requires_grad):
+        return _GConv.apply(x, conv.weight, conv, stats, shift)
+    sh, sw, ph, pw = conv.kgeom
+    return K(x).gconv_fwd(x, weight_of(conv.weight), sh, sw, ph, pw, _or_empty(stats, x),
+                          _or_empty(shift, x))
+
+
+def gconv_bn_act(x, conv, bn, relu: bool = True):
+    """relu?(bn(gconv(x))): train mode takes the BN statistics from the conv's epilogue."""
+    if bn.training:
+        stats = torch.empty(2, conv.out_channels, device=x.device, dtype=torch.float32)
+        z = gconv(x, conv, stats, None if _NO_SHIFT else bn.running_mean)
+        return bn_act(z, bn, relu=relu, stats=stats)
+    return bn_act(gconv(x, conv), bn, relu=relu)
+
+
 # =========================================================================== standalone BN
 class _BNAct(torch.autograd.Function):
     @staticmethod

@@ -270,6 +270,44 @@ def act_gate_bwd_dx(du, z, aff, act, gate, dpool, mean, rstd, gamma, sums):
     return g.reshape(z.shape).to(z.dtype)
 
 
+# --------------------------------------------------------------------------- grouped conv
+def _g_oihw(w):
+    """Stored grouped weight [C, R, S, Cg] -> OIHW [C, Cg, R, S] in fp32."""
+    return _f(w).permute(0, 3, 1, 2).contiguous()
+
+
+def gconv_fwd(x, w, sh, sw, ph, pw, stats, shift=None):
+    C = x.shape[-1]
+    y = _nhwc(F.conv2d(_nchw(_f(x)), _g_oihw(w), None, (sh, sw), (ph, pw), 1,
+                       C // w.shape[3])).to(x.dtype)
+    st = _opt(stats)
+    if st is not None:  # finalized (mean, biased var) of the stored output
+        yf = y.float().reshape(-1, C)
+        st[0].copy_(yf.mean(0))
+        st[1].copy_(yf.var(0, unbiased=False))
+    return y
+
+
+def gconv_dgrad(dy, w, H, W, sh, sw, ph, pw):
+    N, C = dy.shape[0], dy.shape[3]
+    gi = torch.ops.aten.convolution_backward(
+        _nchw(_f(dy)).contiguous(), torch.empty(N, C, H, W, device=dy.device), _g_oihw(w), None,
+        [sh, sw], [ph, pw], [1, 1], False, [0, 0], C // w.shape[3], [True, False, False])[0]
+    return _nhwc(gi).to(dy.dtype)
+
+
+def gconv_wgrad(dy, x, dw, sh, sw, ph, pw, overwrite=False):
+    C, R, S, Cg = dw.shape
+    gw = torch.ops.aten.convolution_backward(
+        _nchw(_f(dy)).contiguous(), _nchw(_f(x)).contiguous(),
+        torch.empty(C, Cg, R, S, device=dy.device), None, [sh, sw], [ph, pw], [1, 1], False,
+        [0, 0], C // Cg, [False, True, False])[1]
+    if overwrite:
+        dw.copy_(gw.permute(0, 2, 3, 1))
+    else:
+        dw.add_(gw.permute(0, 2, 3, 1))
+
+
 def act_bwd(dy, y, dbias):
     """g = dy * (y > 0) if y given else dy; dbias += sum_rows(g)."""
     g = dy if _opt(y) is None else (_f(dy) * (_f(y) > 0)).to(dy.dtype)
