@@ -581,6 +581,107 @@ void dwconv_wgrad(Tensor dy, Tensor x, Tensor dw, int64_t sh, int64_t sw, int64_
   mpa::dwconv_wgrad(bp(dy), bp(x), g, dw.data_ptr<float>(), overwrite, wsp, cur_stream());
 }
 
+// --------------------------------------- LayerNorm / GELU / layer scale over [..., C] (ln.hip)
+// x / dy / h / y [..., C] bf16 contiguous, rows M = numel / C; parameters [C] fp32.  Anything the
+// kernels do not serve is refused here, before an output exists.
+static mpa::LnGeom ln_geom(const char* op, const Tensor& x, bool row) {
+  CHECK_ACT(x);
+  TORCH_CHECK(x.dim() >= 1, op, ": x must be [..., C]");
+  const int64_t C = x.size(-1);
+  TORCH_CHECK(x.numel() < ((int64_t)1 << 31), op, ": tensor too large (2^31 elements)");
+  const mpa::LnGeom g{(int)(C > 0 ? x.numel() / C : 0), (int)C};
+  const char* err = row ? mpa::ln_geom_error(g) : mpa::ln_col_error(g);
+  TORCH_CHECK(!err, op, ": ", err);
+  TORCH_CHECK(aligned16(x), op, ": x must be 16-byte aligned");
+  return g;
+}
+
+static void ln_same(const char* op, const char* name, const Tensor& t, const Tensor& x) {
+  CHECK_ACT(t);
+  TORCH_CHECK(t.sizes() == x.sizes() && aligned16(t), op, ": ", name, " must have x's shape");
+}
+
+// [C] fp32 operand; optional ones may be empty (absent)
+static float* ln_vec(const char* op, const char* name, const Tensor& t, int64_t C, bool optional) {
+  if (optional && !has(t)) return nullptr;
+  TORCH_CHECK(t.defined() && t.numel() == C, op, ": ", name, " must hold ", C, " floats");
+  return fopt_mut(t);
+}
+
+std::vector<Tensor> ln_fwd(Tensor x, Tensor pre_bias, Tensor gamma, Tensor beta, double eps) {
+  const mpa::LnGeom g = ln_geom("ln_fwd", x, true);
+  const float* pb = ln_vec("ln_fwd", "pre_bias", pre_bias, g.C, true);
+  const float* gm = ln_vec("ln_fwd", "gamma", gamma, g.C, false);
+  const float* bt = ln_vec("ln_fwd", "beta", beta, g.C, false);
+  const c10::OptionalDeviceGuard guard(device_of(x));
+  Tensor y = torch::empty_like(x);
+  Tensor stat = empty_like_shape(x, {g.M, 2}, torch::kFloat32);
+  mpa::ln_fwd(bp(x), pb, gm, bt, (float)eps, g, bpm(y), stat.data_ptr<float>(), cur_stream());
+  return {y, stat};
+}
+
+Tensor ln_bwd(Tensor dy, Tensor x, Tensor pre_bias, Tensor gamma, Tensor stat, Tensor dgamma,
+              Tensor dbeta, Tensor dpre_bias, bool overwrite) {
+  const mpa::LnGeom g = ln_geom("ln_bwd", x, true);
+  ln_same("ln_bwd", "dy", dy, x);
+  const float* pb = ln_vec("ln_bwd", "pre_bias", pre_bias, g.C, true);
+  const float* gm = ln_vec("ln_bwd", "gamma", gamma, g.C, false);
+  TORCH_CHECK(has(stat) && stat.numel() == 2 * (int64_t)g.M, "ln_bwd: stat must be [M, 2]");
+  const float* st = fopt(stat);
+  float* dg = ln_vec("ln_bwd", "dgamma", dgamma, g.C, false);
+  float* db = ln_vec("ln_bwd", "dbeta", dbeta, g.C, false);
+  float* dp = ln_vec("ln_bwd", "dpre_bias", dpre_bias, g.C, true);
+  const c10::OptionalDeviceGuard guard(device_of(x));
+  Tensor dx = torch::empty_like(x);
+  Tensor ws;
+  float* wsp = alloc_ws(ws, x, mpa::ln_bwd_ws_floats(g, dp != nullptr));
+  mpa::ln_bwd(bp(dy), bp(x), pb, gm, st, g, bpm(dx), dg, db, dp, overwrite, wsp, cur_stream());
+  return dx;
+}
+
+Tensor gelu_fwd(Tensor h) {
+  const mpa::LnGeom g = ln_geom("gelu_fwd", h, false);
+  const c10::OptionalDeviceGuard guard(device_of(h));
+  Tensor a = torch::empty_like(h);
+  mpa::gelu_fwd(bp(h), g, bpm(a), cur_stream());
+  return a;
+}
+
+Tensor gelu_bwd(Tensor da, Tensor h, Tensor dbias) {
+  const mpa::LnGeom g = ln_geom("gelu_bwd", h, false);
+  ln_same("gelu_bwd", "da", da, h);
+  float* db = ln_vec("gelu_bwd", "dbias", dbias, g.C, true);
+  const c10::OptionalDeviceGuard guard(device_of(h));
+  Tensor dh = torch::empty_like(h);
+  Tensor ws;
+  float* wsp = db ? alloc_ws(ws, h, mpa::ln_col_ws_floats(g)) : nullptr;
+  mpa::gelu_bwd(bp(da), bp(h), g, bpm(dh), db, wsp, cur_stream());
+  return dh;
+}
+
+Tensor scale_add_fwd(Tensor y, Tensor gamma, Tensor res) {
+  const mpa::LnGeom g = ln_geom("scale_add_fwd", y, false);
+  ln_same("scale_add_fwd", "res", res, y);
+  const float* gm = ln_vec("scale_add_fwd", "gamma", gamma, g.C, false);
+  const c10::OptionalDeviceGuard guard(device_of(y));
+  Tensor out = torch::empty_like(y);
+  mpa::scale_add_fwd(bp(y), gm, bp(res), g, bpm(out), cur_stream());
+  return out;
+}
+
+Tensor scale_add_bwd(Tensor dout, Tensor y, Tensor gamma, Tensor dgamma, bool overwrite) {
+  const mpa::LnGeom g = ln_geom("scale_add_bwd", y, false);
+  ln_same("scale_add_bwd", "dout", dout, y);
+  const float* gm = ln_vec("scale_add_bwd", "gamma", gamma, g.C, false);
+  float* dg = ln_vec("scale_add_bwd", "dgamma", dgamma, g.C, false);
+  const c10::OptionalDeviceGuard guard(device_of(y));
+  Tensor dy = torch::empty_like(y);
+  Tensor ws;
+  float* wsp = alloc_ws(ws, y, mpa::ln_col_ws_floats(g));
+  mpa::scale_add_bwd(bp(dout), bp(y), gm, g, bpm(dy), dg, overwrite, wsp, cur_stream());
+  return dy;
+}
+
 // ------------------------------------------------- squeeze-excite / activation gate (se.hip)
 // z / du [N, H, W, C] bf16 (or [B, C]: one "image" of B pixels), aff [2, C] fp32, act 0 | 1 | 2;
 // per-image operands (gate, dpool, pooled, ...) [N, C] fp32.  Anything else is refused.
@@ -2339,6 +2440,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("sh"), py::arg("sw"), py::arg("ph"), py::arg("pw"), py::arg("accum") = py::none());
   m.def("dwconv_wgrad", &dwconv_wgrad, py::arg("dy"), py::arg("x"), py::arg("dw"), py::arg("sh"),
         py::arg("sw"), py::arg("ph"), py::arg("pw"), py::arg("overwrite") = false);
+  m.def("ln_fwd", &ln_fwd, py::arg("x"), py::arg("pre_bias"), py::arg("gamma"), py::arg("beta"),
+        py::arg("eps"), "(y, stat): LayerNorm of x + pre_bias over the last axis; stat [M, 2] (mean, rstd)");
+  m.def("ln_bwd", &ln_bwd, py::arg("dy"), py::arg("x"), py::arg("pre_bias"), py::arg("gamma"),
+        py::arg("stat"), py::arg("dgamma"), py::arg("dbeta"), py::arg("dpre_bias"),
+        py::arg("overwrite") = false);
+  m.def("gelu_fwd", &gelu_fwd, py::arg("h"), "exact (erf) GELU");
+  m.def("gelu_bwd", &gelu_bwd, py::arg("da"), py::arg("h"), py::arg("dbias"),
+        "dh = da gelu'(h); dbias += column sums of dh");
+  m.def("scale_add_fwd", &scale_add_fwd, py::arg("y"), py::arg("gamma"), py::arg("res"),
+        "res + gamma[c] y");
+  m.def("scale_add_bwd", &scale_add_bwd, py::arg("dout"), py::arg("y"), py::arg("gamma"),
+        py::arg("dgamma"), py::arg("overwrite") = false);
   m.def("act_pool", &act_pool, py::arg("z"), py::arg("aff"), py::arg("act"),
         "[N, C] mean over H x W of act(aff[0] z + aff[1]) (act 0 identity, 1 ReLU, 2 hardswish)");
   m.def("se_gate", &se_gate, py::arg("pooled"), py::arg("w1"), py::arg("b1"), py::arg("w2"),

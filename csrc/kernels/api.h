@@ -11,6 +11,7 @@
 #include "dw_plan.h"
 #include "gconv_plan.h"
 #include "se_plan.h"
+#include "ln_plan.h"
 
 namespace mpa {
 
@@ -122,6 +123,29 @@ void dwconv_dgrad(const bf16_raw* dy, const bf16_raw* w, const DwGeom& g, bf16_r
 int64_t dwconv_wgrad_ws_floats(const DwGeom& g);
 void dwconv_wgrad(const bf16_raw* dy, const bf16_raw* x, const DwGeom& g, float* dw,
                   bool overwrite, float* ws, hipStream_t s);
+
+// ln.hip: channels-last LayerNorm, exact GELU and layer scale with residual add, planned by
+// ln_plan.h.  Rows [M][C] bf16, fp32 parameters; no float atomics in any mode.
+// t = x + pre_bias[c] (pre_bias optional); y = (t - mean) rstd gamma[c] + beta[c]; stat [M][2]
+// receives (mean, rstd) of t (ln_geom_error(g) == nullptr)
+void ln_fwd(const bf16_raw* x, const float* pre_bias, const float* gamma, const float* beta,
+            float eps, const LnGeom& g, bf16_raw* y, float* stat, hipStream_t s);
+// dx = rstd (g - mean_c(g) - xhat mean_c(g xhat)), g = dy gamma; dgamma, dbeta and (optional)
+// dpre_bias [C] (+)= the column sums of dy xhat, dy and the stored dx; ws holds
+// ln_bwd_ws_floats(g, dpre_bias != nullptr) floats
+void ln_bwd(const bf16_raw* dy, const bf16_raw* x, const float* pre_bias, const float* gamma,
+            const float* stat, const LnGeom& g, bf16_raw* dx, float* dgamma, float* dbeta,
+            float* dpre_bias, bool overwrite, float* ws, hipStream_t s);
+// a = h Phi(h) (erf form); dh = da (Phi(h) + h phi(h)), dbias [C] (optional) += column sums of
+// the stored dh; ws holds ln_col_ws_floats(g) floats when dbias is set (ln_col_error(g) == nullptr)
+void gelu_fwd(const bf16_raw* h, const LnGeom& g, bf16_raw* a, hipStream_t s);
+void gelu_bwd(const bf16_raw* da, const bf16_raw* h, const LnGeom& g, bf16_raw* dh, float* dbias,
+              float* ws, hipStream_t s);
+// out = res + gamma[c] y; dy = gamma[c] dout, dgamma [C] (+)= column sums of dout y
+void scale_add_fwd(const bf16_raw* y, const float* gamma, const bf16_raw* res, const LnGeom& g,
+                   bf16_raw* out, hipStream_t s);
+void scale_add_bwd(const bf16_raw* dout, const bf16_raw* y, const float* gamma, const LnGeom& g,
+                   bf16_raw* dy, float* dgamma, bool overwrite, float* ws, hipStream_t s);
 
 // se.hip: squeeze-excite and activation-gate kernels, planned by se_plan.h.  z / du / u / dz
 // [N][HW][C] bf16, C % 8 == 0 (se_geom_error(g) == nullptr); t = aff[c] z + aff[C + c] in fp32;

@@ -1,6 +1,6 @@
 // Depthwise convolution for gfx950: forward (with the BN statistics of the stored output from
-// the epilogue), input gradient and weight gradient.  NHWC bf16, C % 8 == 0, k in {3, 5},
-// stride in {1, 2}, padding k / 2, weight stored [C][k][k] (layers.Conv2d groups == C).
+// the epilogue), input gradient and weight gradient.  NHWC bf16, C % 8 == 0, k in {3, 5, 7},
+// stride in {1, 2} (7 x 7: stride 1), padding k / 2, weight stored [C][k][k] (layers.Conv2d groups == C).
 //
 // A depthwise conv does k^2 MACs per loaded element: it is bound by memory and LDS, and an
 // MFMA formulation would be block-diagonal (1/16 of the array busy).  So these are VALU
@@ -335,6 +335,7 @@ template <bool DG>
 void dw_conv_dispatch(const DwGeom& g, const DwArgs& a, const DwPlan& p, hipStream_t s) {
   if (g.k == 3 && g.s == 1) dw_launch(dw_conv_kernel<3, 1, DG>, a, p, s);
   else if (g.k == 3) dw_launch(dw_conv_kernel<3, 2, DG>, a, p, s);
+  else if (g.k == 7) dw_launch(dw_conv_kernel<7, 1, DG>, a, p, s);
   else if (g.s == 1) dw_launch(dw_conv_kernel<5, 1, DG>, a, p, s);
   else dw_launch(dw_conv_kernel<5, 2, DG>, a, p, s);
 }
@@ -383,6 +384,7 @@ void dwconv_wgrad(const bf16_raw* dy, const bf16_raw* x, const DwGeom& g, float*
   a.slab = ws;
   if (g.k == 3 && g.s == 1) dw_launch(dw_wgrad_kernel<3, 1>, a, p, s);
   else if (g.k == 3) dw_launch(dw_wgrad_kernel<3, 2>, a, p, s);
+  else if (g.k == 7) dw_launch(dw_wgrad_kernel<7, 1>, a, p, s);
   else if (g.s == 1) dw_launch(dw_wgrad_kernel<5, 1>, a, p, s);
   else dw_launch(dw_wgrad_kernel<5, 2>, a, p, s);
   const int W = g.C * g.k * g.k;

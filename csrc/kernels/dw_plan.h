@@ -14,6 +14,7 @@ namespace mpa {
 constexpr int DW_THREADS = 256;
 constexpr int DW_STRIP = 4;           // adjacent output columns one thread computes (fwd / dgrad)
 constexpr int DW_MAX_CVB = 8;         // channel vectors per block (128 B per pixel)
+constexpr int DW_MAX_CVB7 = 6;        // 7 x 7: a 16 x 16 tile's 22 x 22 halo fits the LDS budget
 constexpr int DW_LDS_BUDGET = 64 * 1024;  // two blocks per CU
 constexpr int DW_FILL_BLOCKS = 512;   // prefer the smaller tile below two blocks per CU
 constexpr int DW_WGRAD_BLOCKS = 2048;  // weight gradient: images are grouped above this grid
@@ -22,7 +23,7 @@ enum DwKind { DW_FWD = 0, DW_DGRAD = 1, DW_WGRAD = 2 };
 
 struct DwGeom {
   int N, H, W, C;  // the conv's input x
-  int k, s;        // kernel size (3 | 5), stride (1 | 2); padding k / 2
+  int k, s;        // kernel size (3 | 5 | 7), stride (1 | 2; 7 x 7: 1); padding k / 2
 };
 
 struct DwPlan {
@@ -44,8 +45,9 @@ inline int dw_out(int n, int k, int s) { return (n + 2 * (k / 2) - k) / s + 1; }
 inline const char* dw_geom_error(const DwGeom& g) {
   if (g.N < 1 || g.H < 1 || g.W < 1 || g.C < 8) return "empty tensor";
   if (g.C % 8) return "channels must be a multiple of 8";
-  if (g.k != 3 && g.k != 5) return "kernel size must be 3 or 5";
+  if (g.k != 3 && g.k != 5 && g.k != 7) return "kernel size must be 3, 5 or 7";
   if (g.s != 1 && g.s != 2) return "stride must be 1 or 2";
+  if (g.k == 7 && g.s != 1) return "a 7 x 7 kernel runs at stride 1 only";
   if (dw_out(g.H, g.k, g.s) < 1 || dw_out(g.W, g.k, g.s) < 1) return "empty output";
   if ((int64_t)g.N * g.H * g.W * g.C >= (int64_t)1 << 31) return "tensor too large (2^31 elements)";
   return nullptr;
@@ -90,7 +92,11 @@ inline DwPlan dw_plan(int kind, const DwGeom& g) {
   p.SH = dg ? P : g.H;
   p.SW = dg ? Q : g.W;
   const int cv = g.C / 8;
-  p.chunks = (cv + DW_MAX_CVB - 1) / DW_MAX_CVB;
+  // 7 x 7: at 8 vectors a 16 x 16 tile stages 22 x 22 x 128 B + 6 KiB of weights, over the
+  // budget, and the 8 x 8 fallback stages 3.06 x its own pixels against 1.89 x; at 6 vectors
+  // (96 channels, ConvNeXt's widths are multiples) the large tile takes 51 KiB
+  const int max_cvb = g.k == 7 ? DW_MAX_CVB7 : DW_MAX_CVB;
+  p.chunks = (cv + max_cvb - 1) / max_cvb;
   p.cvb = (cv + p.chunks - 1) / p.chunks;  // even split: 9 vectors run as 5 + 4, not 8 + 1
   static const int cand[2][2] = {{16, 16}, {8, 8}};
   for (int i = 0; i < 2; ++i) {

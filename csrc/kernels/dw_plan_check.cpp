@@ -58,7 +58,7 @@ int main() {
   static const int chans[] = {8, 24, 32, 48, 72, 120, 144, 240, 480, 576, 1152, 4096};
   static const int batch[] = {1, 2, 5, 64, 256};
   for (int kind = 0; kind < 3; ++kind)
-    for (int k = 3; k <= 5; k += 2)
+    for (int k = 3; k <= 7; k += 2)
       for (int s = 1; s <= 2; ++s)
         for (int H : sizes)
           for (int W : sizes)
@@ -74,7 +74,16 @@ int main() {
     const DwGeom a{256, 7, 7, 1152, 3, 1}, b{256, 14, 14, 576, 5, 1};
     if (dw_plan(kind, a).grid < 512 || dw_plan(kind, b).grid < 512) return std::printf("grid\n"), 1;
   }
-  const DwGeom bad[] = {{1, 8, 8, 12, 3, 1}, {1, 8, 8, 8, 7, 1}, {1, 8, 8, 8, 3, 3}, {1, 8, 8, 0, 3, 1}};
+  // ConvNeXt's 7 x 7 layers at the training batch: forward and dgrad keep the 16 x 16 tile
+  for (int kind = 0; kind < 2; ++kind) {
+    const DwGeom a{256, 56, 56, 96, 7, 1}, b{256, 28, 28, 192, 7, 1};
+    check(kind, a);
+    check(kind, b);
+    if (dw_plan(kind, a).th != 16 || dw_plan(kind, b).th != 16 || dw_plan(kind, b).cvb != 6)
+      return std::printf("7x7 tile\n"), 1;
+  }
+  const DwGeom bad[] = {{1, 8, 8, 12, 3, 1}, {1, 8, 8, 8, 9, 1}, {1, 8, 8, 8, 7, 2},
+                        {1, 8, 8, 8, 3, 3}, {1, 8, 8, 0, 3, 1}};
   for (const DwGeom& g : bad)
     if (!dw_geom_error(g)) return std::printf("accepted a refused geometry\n"), 1;
   std::printf("dw_plan_check sweep ok: %ld plans\n", n);

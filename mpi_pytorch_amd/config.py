@@ -21,7 +21,8 @@ from dataclasses import dataclass, field, fields
 from typing import Any, Dict, List, Optional
 
 MODEL_NAMES = ("resnet18", "resnet34", "alexnet", "vgg", "vgg16", "squeezenet",
-               "densenet", "inception", "mnasnet", "mobilenet_v3", "resnext50")
+               "densenet", "inception", "mnasnet", "mobilenet_v3", "resnext50",
+               "convnext")
 
 _ENV_PREFIX = "MPA_"
 

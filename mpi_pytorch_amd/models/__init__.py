@@ -30,6 +30,7 @@ from .densenet import densenet121, DenseNet
 from .inception import inception_v3, Inception3, InceptionOutputs
 from .mnasnet import mnasnet1_0, MNASNet
 from .mobilenetv3 import mobilenet_v3_large, MobileNetV3
+from .convnext import convnext_tiny, ConvNeXt
 
 ARCH = {
     "resnet18": ("resnet18", resnet18, 224),
@@ -58,6 +59,12 @@ GROUPED_ARCH = {
     "resnext50": ("resnext50_32x4d", resnext50_32x4d, 224),
 }
 
+# Architectures on the LayerNorm / GELU / layer-scale kernels (ln.hip), looked up after
+# GROUPED_ARCH.
+LN_ARCH = {
+    "convnext": ("convnext_tiny", convnext_tiny, 224),
+}
+
 
 def set_parameter_requires_grad(model: nn.Module, feature_extracting: bool) -> None:
     if feature_extracting:
@@ -79,7 +86,7 @@ def _maybe_pretrained(model: nn.Module, arch: str) -> None:
 def initialize_model(model_name: str, num_classes: int, feature_extract: bool,
                      use_pretrained: bool = False) -> Tuple[nn.Module, int]:
     entry = (ARCH.get(model_name) or EXTRA_ARCH.get(model_name) or SE_ARCH.get(model_name)
-             or GROUPED_ARCH.get(model_name))
+             or GROUPED_ARCH.get(model_name) or LN_ARCH.get(model_name))
     if entry is None:
         raise ValueError("Invalid model name {!r}".format(model_name))
     arch, ctor, input_size = entry
@@ -102,6 +109,8 @@ def initialize_model(model_name: str, num_classes: int, feature_extract: bool,
         model.classifier[1] = Linear(model.classifier[1].in_features, num_classes)
     elif model_name == "mobilenet_v3":
         model.classifier[3] = Linear(model.classifier[3].in_features, num_classes)
+    elif model_name == "convnext":
+        model.classifier[2] = Linear(model.classifier[2].in_features, num_classes)
     return model, input_size
 
 
@@ -125,7 +134,7 @@ def head_parameters(model: nn.Module):
 
 
 __all__ = ["initialize_model", "set_parameter_requires_grad", "ARCH", "EXTRA_ARCH", "SE_ARCH",
-           "GROUPED_ARCH", "InceptionOutputs", "mnasnet1_0", "mobilenet_v3_large",
+           "GROUPED_ARCH", "LN_ARCH", "convnext_tiny", "InceptionOutputs", "mnasnet1_0", "mobilenet_v3_large",
            "resnext50_32x4d",
            "input_spec",
            "resnet18", "resnet34", "vgg11_bn", "vgg16", "alexnet", "squeezenet1_0",

@@ -421,6 +421,32 @@ class Hardswish(nn.Module):
         return Fn.hardswish(x)
 
 
+class LayerNorm(nn.Module):
+    """LayerNorm over the last (channel) axis of an NHWC or [rows, C] activation: torchvision's
+    ``LayerNorm2d`` (which normalises NCHW's channel axis) and ``nn.LayerNorm(C)`` alike, with
+    their parameter names."""
+
+    def __init__(self, normalized_shape: int, eps: float = 1e-6):
+        super().__init__()
+        self.normalized_shape = (int(normalized_shape),)
+        self.eps = eps
+        self.weight = nn.Parameter(torch.ones(normalized_shape))
+        self.bias = nn.Parameter(torch.zeros(normalized_shape))
+
+    def forward(self, x):
+        return Fn.layer_norm(x, self)
+
+    def extra_repr(self):
+        return "{}, eps={}".format(self.normalized_shape, self.eps)
+
+
+class GELU(nn.Module):
+    """Exact (erf) GELU.  Behind a Linear the models fuse it into ``Fn.linear_gelu``."""
+
+    def forward(self, x):
+        return Fn.gelu(x)
+
+
 class SqueezeExcitation(nn.Module):
     """torchvision's SqueezeExcitation: ``fc1`` / ``fc2`` are 1x1 convs with bias (OIHW in the
     state_dict), ReLU after the first and hardsigmoid after the second.  It has no forward of

@@ -994,6 +994,146 @@ def dwconv_bn_act(x, conv, bn, relu: bool = True):
     return bn_act(dwconv(x, conv), bn, relu=relu)
 
 
+# ========================================= LayerNorm / GELU / layer scale (ConvNeXt, ln.hip)
+class _LayerNorm(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, w, b, pre, eps):
+        y, stat = K(x).ln_fwd(x, _or_empty(pre, x), w, b, eps)
+        ctx.params = (w, b, pre)
+        ctx.save_for_backward(x, stat)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, stat = ctx.saved_tensors
+        w, b, pre = ctx.params
+        k = K(dy)
+        dy = dy.contiguous()
+        ps = [p for p in (w, b, pre) if p is not None]
+        if not all(p.requires_grad for p in ps):  # frozen: gradients into scratch
+            tmp = torch.empty(3, x.shape[-1], device=x.device, dtype=torch.float32)
+            dx = k.ln_bwd(dy, x, _or_empty(pre, x), w, stat, tmp[0], tmp[1], _empty(x), True)
+            return _grads(_LayerNorm, dx)
+        # dx on the compute stream (the chain waits for it) with the parameter gradients: one
+        # kernel produces both, so nothing is left for the side stream
+        fresh = [_fresh(p) for p in ps]
+        dx = k.ln_bwd(dy, x, _or_empty(pre, x), w, stat, grad_sink(w), grad_sink(b),
+                      _sink(pre, x), all(fresh))
+        _done(*ps)
+        return _grads(_LayerNorm, dx)
+
+
+def layer_norm(x, ln, pre_bias: Optional[torch.nn.Parameter] = None):
+    """LayerNorm over the last (channel) axis of ``x + pre_bias``; ``pre_bias`` is the bias of the
+    depthwise conv that produced ``x``, added in the kernel's registers."""
+    if torch.is_grad_enabled() and (ln.weight.requires_grad or x.requires_grad):
+        return _LayerNorm.apply(x, ln.weight, ln.bias, pre_bias, ln.eps)
+    return K(x).ln_fwd(x, _or_empty(pre_bias, x), ln.weight, ln.bias, ln.eps)[0]
+
+
+def dwconv_ln(x, conv, ln, join: Optional[GradJoin] = None):
+    """ln(dwconv(x) + conv.bias): the conv runs bias-free and the LayerNorm kernel adds the bias."""
+    if not conv.depthwise:
+        raise ValueError("dwconv_ln: a depthwise Conv2d (groups == channels) expected")
+    if torch.is_grad_enabled() and (conv.weight.requires_grad or x.requires_grad):
+        z = _DwConv.apply(x, conv.weight, conv, None, None, join)
+    else:
+        sh, sw, ph, pw = conv.kgeom
+        z = K(x).dwconv_fwd(x, weight_of(conv.weight), sh, sw, ph, pw, _empty(x), _empty(x))
+    return layer_norm(z, ln, conv.bias)
+
+
+class _Gelu(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, h):
+        ctx.save_for_backward(h)
+        return K(h).gelu_fwd(h)
+
+    @staticmethod
+    def backward(ctx, da):
+        (h,) = ctx.saved_tensors
+        return K(da).gelu_bwd(da.contiguous(), h, _empty(da))
+
+
+def gelu(x):
+    """Exact (erf) GELU, ``nn.GELU()``."""
+    if torch.is_grad_enabled() and x.requires_grad:
+        return _Gelu.apply(x)
+    return K(x).gelu_fwd(x)
+
+
+class _LinearGelu(torch.autograd.Function):
+    """gelu(x W^T + b): the pre-activation is kept, and the GELU backward reduces the bias
+    gradient from the dh it stores (the role ``act_bwd`` plays for ReLU)."""
+
+    @staticmethod
+    def forward(ctx, x, w, b):
+        k = K(x)
+        h = k.linear_fwd(x, weight_of(w), _or_empty(b, x), False)
+        ctx.params = (w, b)
+        ctx.save_for_backward(x, h)
+        return k.gelu_fwd(h)
+
+    @staticmethod
+    def backward(ctx, da):
+        x, h = ctx.saved_tensors
+        w, b = ctx.params
+        k = K(da)
+        g = k.gelu_bwd(da.contiguous(), h, _sink(b, da))
+        dx = (k.linear_dgrad(g, weight_of(w), weight_t_of(w)) if ctx.needs_input_grad[0]
+              else None)
+        _done(b)
+        if w.requires_grad:
+            k.linear_wgrad(g, x, w.grad, overwrite=_fresh(w))
+            _done(w)
+        return dx, None, None
+
+
+def linear_gelu(x, lin):
+    """gelu(lin(x)) over rows [M, in]; the layer's output width must be stored unpadded."""
+    if lin.weight.shape[0] != lin.out_features:
+        raise ValueError("linear_gelu: out_features must be a multiple of 32")
+    if torch.is_grad_enabled() and (lin.weight.requires_grad or x.requires_grad):
+        return _LinearGelu.apply(x, lin.weight, lin.bias)
+    k = K(x)
+    return k.gelu_fwd(k.linear_fwd(x, weight_of(lin.weight), _or_empty(lin.bias, x), False))
+
+
+class _ScaleResidual(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, y, gamma, res, join=None):
+        ctx.gamma, ctx.join = gamma, join
+        ctx.save_for_backward(y)
+        return K(y).scale_add_fwd(y, gamma, res)
+
+    @staticmethod
+    def backward(ctx, dout):
+        (y,) = ctx.saved_tensors
+        gamma = ctx.gamma
+        k = K(dout)
+        dout = dout.contiguous()
+        if gamma.requires_grad:
+            dy = k.scale_add_bwd(dout, y, gamma, grad_sink(gamma), _fresh(gamma))
+            _done(gamma)
+        else:
+            dy = k.scale_add_bwd(dout, y, gamma, torch.empty_like(gamma, dtype=torch.float32),
+                                 True)
+        # the residual's gradient is dout itself: through the join it becomes the accumulate
+        # operand of the block's depthwise dgrad, no add pass
+        dres = None
+        if ctx.needs_input_grad[2]:
+            dres = dout if ctx.join is None else ctx.join.add(k, dout)
+        return dy, None, dres, None
+
+
+def scale_residual(y, gamma, res, join: Optional[GradJoin] = None):
+    """res + gamma[c] * y (ConvNeXt's layer scale and residual add); ``join``: res's gradient is
+    summed with its other consumers' (GradJoin)."""
+    if torch.is_grad_enabled() and (gamma.requires_grad or y.requires_grad or res.requires_grad):
+        return _ScaleResidual.apply(y, gamma, res, join)
+    return K(y).scale_add_fwd(y, gamma, res)
+
+
 # ================================================== BN -> activation -> squeeze-excite gate
 ACT_NONE, ACT_RELU, ACT_HARDSWISH = 0, 1, 2
 

@@ -171,6 +171,70 @@ def dwconv_wgrad(dy, x, dw, sh, sw, ph, pw, overwrite=False):
         dw.add_(gw.permute(0, 2, 3, 1))
 
 
+# ------------------------------------------- LayerNorm / GELU / layer scale over [..., C]
+def _ln_t(x, pre_bias):
+    pb = _opt(pre_bias)
+    return _f(x) if pb is None else _f(x) + pb
+
+
+def ln_fwd(x, pre_bias, gamma, beta, eps):
+    """(y, stat): LayerNorm of t = x + pre_bias over the last axis with the centred (two-pass)
+    variance; stat [M, 2] = (mean, rstd) of t."""
+    t = _ln_t(x, pre_bias)
+    mean = t.mean(-1, keepdim=True)
+    d = t - mean
+    rstd = 1.0 / torch.sqrt((d * d).mean(-1, keepdim=True) + eps)
+    y = (d * rstd * gamma + beta).to(x.dtype)
+    return y, torch.cat([mean, rstd], -1).reshape(-1, 2)
+
+
+def _acc(dst, val, overwrite):
+    if overwrite:
+        dst.copy_(val)
+    else:
+        dst.add_(val)
+
+
+def ln_bwd(dy, x, pre_bias, gamma, stat, dgamma, dbeta, dpre_bias, overwrite=False):
+    C = x.shape[-1]
+    st = stat.reshape(x.shape[:-1] + (2,))
+    xh = (_ln_t(x, pre_bias) - st[..., :1]) * st[..., 1:]
+    dyf = _f(dy)
+    g = dyf * gamma
+    dx = (st[..., 1:] * (g - g.mean(-1, keepdim=True) - xh * (g * xh).mean(-1, keepdim=True))
+          ).to(dy.dtype)
+    _acc(dgamma, (dyf * xh).reshape(-1, C).sum(0), overwrite)
+    _acc(dbeta, dyf.reshape(-1, C).sum(0), overwrite)
+    if _opt(dpre_bias) is not None:
+        _acc(dpre_bias, _f(dx).reshape(-1, C).sum(0), overwrite)
+    return dx
+
+
+def gelu_fwd(h):
+    return F.gelu(_f(h)).to(h.dtype)
+
+
+def gelu_bwd(da, h, dbias):
+    """dh = da (Phi(h) + h phi(h)); dbias (optional) += column sums of the stored dh."""
+    hf = _f(h)
+    cdf = 0.5 * (1.0 + torch.erf(hf * 0.7071067811865476))
+    pdf = torch.exp(-0.5 * hf * hf) * 0.3989422804014327
+    dh = (_f(da) * (cdf + hf * pdf)).to(da.dtype)
+    db = _opt(dbias)
+    if db is not None:
+        db.add_(_f(dh).reshape(-1, dh.shape[-1]).sum(0))
+    return dh
+
+
+def scale_add_fwd(y, gamma, res):
+    return torch.addcmul(_f(res), _f(y), gamma).to(y.dtype)
+
+
+def scale_add_bwd(dout, y, gamma, dgamma, overwrite=False):
+    _acc(dgamma, (_f(dout) * _f(y)).reshape(-1, y.shape[-1]).sum(0), overwrite)
+    return (_f(dout) * gamma).to(dout.dtype)
+
+
 # ------------------------------------------------------- squeeze-excite / activation gate
 def _se_t(z, aff):
     """t = aff[0] z + aff[1] as one rounding of the exact value (the kernels' fused
