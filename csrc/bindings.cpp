@@ -682,6 +682,113 @@ Tensor scale_add_bwd(Tensor dout, Tensor y, Tensor gamma, Tensor dgamma, bool ov
   return dy;
 }
 
+// ----------------------------------------- multi-head attention and ViT tokens (attn.hip)
+// qkv [B, S, 3, H, 64] (or [B, S, 3 H 64] with heads given) bf16 contiguous.  Anything the
+// kernels do not serve is refused here, before an output exists.
+static mpa::AttnGeom attn_geom(const char* op, const Tensor& qkv, int64_t heads) {
+  CHECK_ACT(qkv);
+  TORCH_CHECK(qkv.dim() == 5 || (qkv.dim() == 3 && heads > 0), op,
+              ": qkv must be [B, S, 3, H, 64], or [B, S, 3 H 64] with heads");
+  const int64_t H = qkv.dim() == 5 ? qkv.size(3) : heads;
+  if (qkv.dim() == 5) {
+    TORCH_CHECK(qkv.size(2) == 3, op, ": qkv must hold q, k and v");
+    TORCH_CHECK(qkv.size(4) == mpa::AT_D, op, ": head dim must be 64, got ", qkv.size(4));
+    TORCH_CHECK(heads <= 0 || heads == H, op, ": heads does not match qkv");
+  } else {
+    TORCH_CHECK(qkv.size(2) == 3 * H * mpa::AT_D, op, ": last dimension must be 3 * heads * 64, got ",
+                qkv.size(2));
+  }
+  TORCH_CHECK(qkv.size(0) < ((int64_t)1 << 31) && qkv.size(1) < ((int64_t)1 << 31) &&
+                  H < ((int64_t)1 << 31), op, ": tensor too large");
+  const mpa::AttnGeom g{(int)qkv.size(0), (int)qkv.size(1), (int)H};
+  const char* err = mpa::attn_geom_error(g);
+  TORCH_CHECK(!err, op, ": ", err);
+  TORCH_CHECK(aligned16(qkv), op, ": qkv must be 16-byte aligned");
+  return g;
+}
+
+std::vector<Tensor> attn_fwd(Tensor qkv, int64_t heads) {
+  const mpa::AttnGeom g = attn_geom("attn_fwd", qkv, heads);
+  const c10::OptionalDeviceGuard guard(device_of(qkv));
+  Tensor o = empty_like_shape(qkv, {g.B, g.S, (int64_t)g.H * mpa::AT_D}, torch::kBFloat16);
+  Tensor lse = empty_like_shape(qkv, {g.B, g.H, g.S}, torch::kFloat32);
+  mpa::attn_fwd(bp(qkv), g, bpm(o), lse.data_ptr<float>(), cur_stream());
+  return {o, lse};
+}
+
+Tensor attn_bwd(Tensor d_o, Tensor qkv, Tensor o, Tensor lse, int64_t heads) {
+  const mpa::AttnGeom g = attn_geom("attn_bwd", qkv, heads);
+  CHECK_ACT(d_o);
+  CHECK_ACT(o);
+  const int64_t n = (int64_t)g.B * g.S * g.H * mpa::AT_D;
+  TORCH_CHECK(d_o.numel() == n && o.numel() == n && aligned16(d_o) && aligned16(o),
+              "attn_bwd: do and o must be [B, S, H 64]");
+  TORCH_CHECK(has(lse) && lse.numel() == (int64_t)g.B * g.H * g.S, "attn_bwd: lse must be [B, H, S]");
+  const float* lp = fopt(lse);
+  const c10::OptionalDeviceGuard guard(device_of(qkv));
+  Tensor dqkv = torch::empty_like(qkv);
+  mpa::attn_bwd(bp(d_o), bp(qkv), bp(o), lp, g, bpm(dqkv), cur_stream());
+  return dqkv;
+}
+
+Tensor patchify(Tensor x, int64_t P) {
+  CHECK_ACT(x);
+  TORCH_CHECK(x.dim() == 4 && P > 0 && P < 65536, "patchify: x must be NHWC, P > 0");
+  TORCH_CHECK(x.numel() < ((int64_t)1 << 31), "patchify: tensor too large (2^31 elements)");
+  const mpa::PatchGeom g{(int)x.size(0), (int)x.size(1), (int)x.size(2), (int)x.size(3), (int)P};
+  const char* err = mpa::patch_geom_error(g);
+  TORCH_CHECK(!err, "patchify: ", err);
+  TORCH_CHECK(aligned16(x), "patchify: x must be 16-byte aligned");
+  const c10::OptionalDeviceGuard guard(device_of(x));
+  Tensor rows = empty_like_shape(x, {(int64_t)g.B * (g.Hi / g.P) * (g.Wi / g.P), (int64_t)g.P * g.P * g.Cp},
+                                 torch::kBFloat16);
+  mpa::patchify(bp(x), g, bpm(rows), cur_stream());
+  return rows;
+}
+
+static const float* tok_vec(const char* op, const char* name, const Tensor& t, int64_t n) {
+  TORCH_CHECK(t.defined() && t.numel() == n, op, ": ", name, " must hold ", n, " floats");
+  const float* p = fopt(t);
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(p) % 16 == 0, op, ": ", name, " must be 16-byte aligned");
+  return p;
+}
+
+Tensor tokens_fwd(Tensor patch, Tensor cls, Tensor pos) {
+  CHECK_ACT(patch);
+  TORCH_CHECK(patch.dim() == 2 && patch.size(1) > 0 && pos.defined() &&
+                  pos.numel() % patch.size(1) == 0,
+              "tokens_fwd: patch rows [B Np, D], pos (1 + Np) D floats");
+  const int64_t D = patch.size(1), T = pos.numel() / D;
+  TORCH_CHECK(T >= 2 && patch.size(0) > 0 && patch.size(0) % (T - 1) == 0 && T < ((int64_t)1 << 31),
+              "tokens_fwd: patch rows must be a multiple of the patches of pos");
+  TORCH_CHECK(patch.size(0) / (T - 1) * T * D < ((int64_t)1 << 31), "tokens_fwd: tensor too large");
+  const mpa::TokGeom g{(int)(patch.size(0) / (T - 1)), (int)T, (int)D};
+  const char* err = mpa::tok_geom_error(g);
+  TORCH_CHECK(!err, "tokens_fwd: ", err);
+  const float* cp = tok_vec("tokens_fwd", "cls", cls, D);
+  const float* pp = tok_vec("tokens_fwd", "pos", pos, T * D);
+  TORCH_CHECK(aligned16(patch), "tokens_fwd: patch must be 16-byte aligned");
+  const c10::OptionalDeviceGuard guard(device_of(patch));
+  Tensor x = empty_like_shape(patch, {g.B, g.T, g.D}, torch::kBFloat16);
+  mpa::tokens_fwd(bp(patch), cp, pp, g, bpm(x), cur_stream());
+  return x;
+}
+
+Tensor tokens_bwd(Tensor dx, Tensor dcls, Tensor dpos, bool overwrite) {
+  CHECK_ACT(dx);
+  TORCH_CHECK(dx.dim() == 3 && dx.numel() < ((int64_t)1 << 31), "tokens_bwd: dx must be [B, T, D]");
+  const mpa::TokGeom g{(int)dx.size(0), (int)dx.size(1), (int)dx.size(2)};
+  const char* err = mpa::tok_geom_error(g);
+  TORCH_CHECK(!err, "tokens_bwd: ", err);
+  float* cp = const_cast<float*>(tok_vec("tokens_bwd", "dcls", dcls, g.D));
+  float* pp = const_cast<float*>(tok_vec("tokens_bwd", "dpos", dpos, (int64_t)g.T * g.D));
+  TORCH_CHECK(aligned16(dx), "tokens_bwd: dx must be 16-byte aligned");
+  const c10::OptionalDeviceGuard guard(device_of(dx));
+  Tensor dpatch = empty_like_shape(dx, {(int64_t)g.B * (g.T - 1), g.D}, torch::kBFloat16);
+  mpa::tokens_bwd(bp(dx), g, bpm(dpatch), cp, pp, overwrite, cur_stream());
+  return dpatch;
+}
+
 // ------------------------------------------------- squeeze-excite / activation gate (se.hip)
 // z / du [N, H, W, C] bf16 (or [B, C]: one "image" of B pixels), aff [2, C] fp32, act 0 | 1 | 2;
 // per-image operands (gate, dpool, pooled, ...) [N, C] fp32.  Anything else is refused.
@@ -2452,6 +2559,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "res + gamma[c] y");
   m.def("scale_add_bwd", &scale_add_bwd, py::arg("dout"), py::arg("y"), py::arg("gamma"),
         py::arg("dgamma"), py::arg("overwrite") = false);
+  m.def("attn_fwd", &attn_fwd, py::arg("qkv"), py::arg("heads") = 0,
+        "(o, lse): softmax(q k^T / 8) v per head of the packed qkv [B, S, 3, H, 64]");
+  m.def("attn_bwd", &attn_bwd, py::arg("do"), py::arg("qkv"), py::arg("o"), py::arg("lse"),
+        py::arg("heads") = 0, "dqkv in qkv's layout");
+  m.def("patchify", &patchify, py::arg("x"), py::arg("P"),
+        "[B Hp Wp, P P C] patch rows of an NHWC image");
+  m.def("tokens_fwd", &tokens_fwd, py::arg("patch"), py::arg("cls"), py::arg("pos"),
+        "[B, 1 + Np, D]: [cls | patch rows] + pos");
+  m.def("tokens_bwd", &tokens_bwd, py::arg("dx"), py::arg("dcls"), py::arg("dpos"),
+        py::arg("overwrite") = false, "dpatch = dx[:, 1:]; dcls, dpos (+)= sums over the batch");
   m.def("act_pool", &act_pool, py::arg("z"), py::arg("aff"), py::arg("act"),
         "[N, C] mean over H x W of act(aff[0] z + aff[1]) (act 0 identity, 1 ReLU, 2 hardswish)");
   m.def("se_gate", &se_gate, py::arg("pooled"), py::arg("w1"), py::arg("b1"), py::arg("w2"),

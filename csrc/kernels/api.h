@@ -12,6 +12,7 @@
 #include "gconv_plan.h"
 #include "se_plan.h"
 #include "ln_plan.h"
+#include "attn_plan.h"
 
 namespace mpa {
 
@@ -146,6 +147,23 @@ void scale_add_fwd(const bf16_raw* y, const float* gamma, const bf16_raw* res, c
                    bf16_raw* out, hipStream_t s);
 void scale_add_bwd(const bf16_raw* dout, const bf16_raw* y, const float* gamma, const LnGeom& g,
                    bf16_raw* dy, float* dgamma, bool overwrite, float* ws, hipStream_t s);
+
+// attn.hip: fused multi-head self-attention over the packed in-projection output
+// qkv [B][S][3][H][64] bf16 (attn_geom_error(g) == nullptr), scale 1/8, no mask, no dropout;
+// planned by attn_plan.h.  o [B][S][H 64] bf16, lse [B][H][S] fp32 (log-sum-exp of the scaled
+// scores).  No float atomics: the backward is two kernels (dK / dV, then dQ).
+void attn_fwd(const bf16_raw* qkv, const AttnGeom& g, bf16_raw* o, float* lse, hipStream_t s);
+// dqkv has qkv's layout and is written whole
+void attn_bwd(const bf16_raw* d_o, const bf16_raw* qkv, const bf16_raw* o, const float* lse,
+              const AttnGeom& g, bf16_raw* dqkv, hipStream_t s);
+// ViT token kernels: rows [B (Hi/P) (Wi/P)][P P Cp] from the NHWC image (patch_geom_error);
+// x [B][T][D] = [cls | patch rows] + pos (fp32 add, one rounding; tok_geom_error);
+// dpatch = dx[:, 1:], dpos [T][D] (+)= sum_b dx, dcls [D] (+)= sum_b dx[:, 0] in batch order
+void patchify(const bf16_raw* x, const PatchGeom& g, bf16_raw* rows, hipStream_t s);
+void tokens_fwd(const bf16_raw* patch, const float* cls, const float* pos, const TokGeom& g,
+                bf16_raw* x, hipStream_t s);
+void tokens_bwd(const bf16_raw* dx, const TokGeom& g, bf16_raw* dpatch, float* dcls, float* dpos,
+                bool overwrite, hipStream_t s);
 
 // se.hip: squeeze-excite and activation-gate kernels, planned by se_plan.h.  z / du / u / dz
 // [N][HW][C] bf16, C % 8 == 0 (se_geom_error(g) == nullptr); t = aff[c] z + aff[C + c] in fp32;

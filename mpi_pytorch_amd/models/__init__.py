@@ -31,6 +31,7 @@ from .inception import inception_v3, Inception3, InceptionOutputs
 from .mnasnet import mnasnet1_0, MNASNet
 from .mobilenetv3 import mobilenet_v3_large, MobileNetV3
 from .convnext import convnext_tiny, ConvNeXt
+from .vit import vit_b_16, VisionTransformer
 
 ARCH = {
     "resnet18": ("resnet18", resnet18, 224),
@@ -65,6 +66,11 @@ LN_ARCH = {
     "convnext": ("convnext_tiny", convnext_tiny, 224),
 }
 
+# Architectures on the fused attention kernels (attn.hip), looked up after LN_ARCH.
+ATTN_ARCH = {
+    "vit": ("vit_b_16", vit_b_16, 224),
+}
+
 
 def set_parameter_requires_grad(model: nn.Module, feature_extracting: bool) -> None:
     if feature_extracting:
@@ -86,7 +92,8 @@ def _maybe_pretrained(model: nn.Module, arch: str) -> None:
 def initialize_model(model_name: str, num_classes: int, feature_extract: bool,
                      use_pretrained: bool = False) -> Tuple[nn.Module, int]:
     entry = (ARCH.get(model_name) or EXTRA_ARCH.get(model_name) or SE_ARCH.get(model_name)
-             or GROUPED_ARCH.get(model_name) or LN_ARCH.get(model_name))
+             or GROUPED_ARCH.get(model_name) or LN_ARCH.get(model_name)
+             or ATTN_ARCH.get(model_name))
     if entry is None:
         raise ValueError("Invalid model name {!r}".format(model_name))
     arch, ctor, input_size = entry
@@ -111,6 +118,8 @@ def initialize_model(model_name: str, num_classes: int, feature_extract: bool,
         model.classifier[3] = Linear(model.classifier[3].in_features, num_classes)
     elif model_name == "convnext":
         model.classifier[2] = Linear(model.classifier[2].in_features, num_classes)
+    elif model_name == "vit":
+        model.heads.head = Linear(model.heads.head.in_features, num_classes)
     return model, input_size
 
 
@@ -127,14 +136,14 @@ def input_spec(model: nn.Module, hw) -> dict:
 
 def head_parameters(model: nn.Module):
     """Parameters of the replaced classifier head(s)."""
-    for name in ("fc", "classifier", "AuxLogits"):
+    for name in ("fc", "classifier", "AuxLogits", "heads"):
         m = getattr(model, name, None)
         if m is not None:
             yield from m.parameters()
 
 
 __all__ = ["initialize_model", "set_parameter_requires_grad", "ARCH", "EXTRA_ARCH", "SE_ARCH",
-           "GROUPED_ARCH", "LN_ARCH", "convnext_tiny", "InceptionOutputs", "mnasnet1_0", "mobilenet_v3_large",
+           "GROUPED_ARCH", "LN_ARCH", "ATTN_ARCH", "convnext_tiny", "vit_b_16", "InceptionOutputs", "mnasnet1_0", "mobilenet_v3_large",
            "resnext50_32x4d",
            "input_spec",
            "resnet18", "resnet34", "vgg11_bn", "vgg16", "alexnet", "squeezenet1_0",

@@ -447,6 +447,103 @@ class GELU(nn.Module):
         return Fn.gelu(x)
 
 
+class _InProj:
+    """The packed q/k/v projection of a MultiheadAttention as the layer ``Fn.linear_act`` reads."""
+
+    def __init__(self, mha):
+        self._mha = mha
+        self.out_features = 3 * mha.embed_dim
+
+    @property
+    def weight(self):
+        return self._mha.in_proj_weight
+
+    @property
+    def bias(self):
+        return self._mha.in_proj_bias
+
+
+class MultiheadAttention(nn.Module):
+    """Self-attention with ``torch.nn.MultiheadAttention``'s parameter names and q/k/v row
+    order: ``in_proj_weight`` [3 D, D], ``in_proj_bias`` [3 D], ``out_proj``.  Head dim 64.  The
+    in-projection's rows [B S, 3 D] are the attention kernel's packed input as they are, and its
+    output [B, S, D] is the out-projection's rows: no permute or split in between."""
+
+    def __init__(self, embed_dim: int, num_heads: int):
+        super().__init__()
+        if embed_dim != 64 * num_heads:
+            raise ValueError("MultiheadAttention: head dim must be 64 (embed_dim = 64 * num_heads)")
+        self.embed_dim, self.num_heads = embed_dim, num_heads
+        self.in_proj_weight = nn.Parameter(torch.empty(3 * embed_dim, embed_dim))
+        self.in_proj_weight._mpa_tlayout = (3 * embed_dim, 1, embed_dim)
+        self.in_proj_bias = nn.Parameter(torch.zeros(3 * embed_dim))
+        self.out_proj = Linear(embed_dim, embed_dim)
+        nn.init.xavier_uniform_(self.in_proj_weight)
+        nn.init.zeros_(self.out_proj.bias)
+        self._in = _InProj(self)
+
+    def forward(self, rows, B: int, S: int):
+        """rows [B S, D] -> [B S, D]"""
+        D = self.embed_dim
+        qkv = Fn.linear_act(rows, self._in).reshape(B, S, 3 * D)
+        o = Fn.attention(qkv, self.num_heads)
+        return Fn.linear_act(o.reshape(B * S, D), self.out_proj)
+
+    def extra_repr(self):
+        return "embed_dim={}, num_heads={}".format(self.embed_dim, self.num_heads)
+
+
+class PatchEmbed(nn.Module):
+    """ViT's patch embedding, a P x P / stride P conv, as patch rows times a [D, P P Cp] matrix
+    (``Fn.patch_tokens``).  The state_dict holds torchvision's ``weight`` [D, C, P, P] and
+    ``bias``; stored (ky, kx, c) with zero columns for the image's pad channels."""
+
+    def __init__(self, in_channels: int, width: int, patch: int, cin_store: int = 8):
+        super().__init__()
+        if width % 32:
+            raise ValueError("PatchEmbed: width must be a multiple of 32")
+        self.in_channels, self.out_features, self.patch, self.cin_store = in_channels, width, patch, cin_store
+        fan_in = in_channels * patch * patch
+        w = torch.empty(width, in_channels, patch, patch)
+        nn.init.trunc_normal_(w, std=math.sqrt(1.0 / fan_in))
+        self.weight = nn.Parameter(self._imp(w).contiguous())
+        self.weight._mpa_export = self._exp
+        self.weight._mpa_import = self._imp
+        self.weight._mpa_tlayout = (width, 1, patch * patch * cin_store)
+        self.bias = nn.Parameter(torch.zeros(width))
+
+    def _exp(self, t):
+        P = self.patch
+        t = t.reshape(t.shape[0], P, P, self.cin_store)[..., :self.in_channels]
+        return t.permute(0, 3, 1, 2)
+
+    def _imp(self, t):
+        t = F.pad(t.permute(0, 2, 3, 1), (0, self.cin_store - self.in_channels))
+        return t.reshape(t.shape[0], -1)
+
+    def _save_to_state_dict(self, destination, prefix, keep_vars):
+        super()._save_to_state_dict(destination, prefix, keep_vars)
+        k = prefix + "weight"
+        if k in destination:
+            w = self._exp(destination[k])
+            destination[k] = w if keep_vars else w.contiguous()
+
+    def _load_from_state_dict(self, state_dict, prefix, *args, **kwargs):
+        k = prefix + "weight"
+        if k in state_dict and state_dict[k].dim() == 4:
+            state_dict[k] = self._imp(state_dict[k])
+        super()._load_from_state_dict(state_dict, prefix, *args, **kwargs)
+
+    def fit_input(self, x):
+        c = x.shape[-1]
+        if c > self.cin_store:
+            raise ValueError("PatchEmbed: %d input channels, %d stored" % (c, self.cin_store))
+        return F.pad(x, (0, self.cin_store - c)) if c < self.cin_store else x
+
+    def extra_repr(self):
+        return "{}, {}, patch={}".format(self.in_channels, self.out_features, self.patch)
+
+
 class SqueezeExcitation(nn.Module):
     """torchvision's SqueezeExcitation: ``fc1`` / ``fc2`` are 1x1 convs with bias (OIHW in the
     state_dict), ReLU after the first and hardsigmoid after the second.  It has no forward of

@@ -1134,6 +1134,116 @@ def scale_residual(y, gamma, res, join: Optional[GradJoin] = None):
     return K(y).scale_add_fwd(y, gamma, res)
 
 
+# ============================================ multi-head attention and ViT tokens (attn.hip)
+class _Attention(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, qkv, heads):
+        o, lse = K(qkv).attn_fwd(qkv, heads)
+        ctx.heads = heads
+        ctx.save_for_backward(qkv, o, lse)
+        return o
+
+    @staticmethod
+    def backward(ctx, do):
+        qkv, o, lse = ctx.saved_tensors
+        return K(do).attn_bwd(do.contiguous(), qkv, o, lse, ctx.heads), None
+
+
+def attention(qkv, heads: int):
+    """Self-attention over the packed in-projection output ``qkv`` [B, S, 3 * heads * 64] (q, k, v
+    row blocks, heads of 64 inside each): [B, S, heads * 64], scale 1/8, no mask, no dropout."""
+    if torch.is_grad_enabled() and qkv.requires_grad:
+        return _Attention.apply(qkv, heads)
+    return K(qkv).attn_fwd(qkv, heads)[0]
+
+
+class _Tokens(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, patch, cls, pos):
+        ctx.params = (cls, pos)
+        return K(patch).tokens_fwd(patch, cls, pos)
+
+    @staticmethod
+    def backward(ctx, dx):
+        cls, pos = ctx.params
+        k = K(dx)
+        dx = dx.contiguous()
+        if not (cls.requires_grad and pos.requires_grad):  # frozen: sums into scratch
+            tmp = torch.empty(cls.numel() + pos.numel(), device=dx.device, dtype=torch.float32)
+            return k.tokens_bwd(dx, tmp[:cls.numel()], tmp[cls.numel():], True), None, None
+        fresh = [_fresh(cls), _fresh(pos)]
+        dpatch = k.tokens_bwd(dx, grad_sink(cls), grad_sink(pos), all(fresh))
+        _done(cls, pos)
+        return dpatch, None, None
+
+
+def patch_tokens(x, embed, cls, pos):
+    """ViT's front end: the NHWC image cut into ``embed.patch``-square patch rows, the patch
+    embedding as a rows GEMM, then [cls | patches] + pos: [B, 1 + Np, D]."""
+    rows = K(x).patchify(x, embed.patch)
+    pr = linear_act(rows, embed)
+    if not pr.is_contiguous():
+        pr = pr.contiguous()
+    if torch.is_grad_enabled() and (pr.requires_grad or cls.requires_grad or pos.requires_grad):
+        return _Tokens.apply(pr, cls, pos)
+    return K(pr).tokens_fwd(pr, cls, pos)
+
+
+class _JoinInput(torch.autograd.Function):
+    """Identity in front of one consumer of an activation whose gradient contributions meet in
+    ``join``: its backward hands the consumer's gradient in."""
+
+    @staticmethod
+    def forward(ctx, x, join):
+        ctx.join = join
+        return x.view_as(x)
+
+    @staticmethod
+    def backward(ctx, g):
+        return ctx.join.add(K(g), g.contiguous()), None
+
+
+class _ResidualAdd(torch.autograd.Function):
+    """y += x in place (``add_bf16_``: fp32 add, one rounding).  dout goes to y's branch as it
+    is and to x through the join, where it meets the gradient of x's other consumer."""
+
+    @staticmethod
+    def forward(ctx, y, x, join):
+        ctx.join = join
+        K(y).add_bf16_(y, x)
+        ctx.mark_dirty(y)
+        return y
+
+    @staticmethod
+    def backward(ctx, dout):
+        dout = dout.contiguous()
+        dres = None
+        if ctx.needs_input_grad[1]:
+            dres = dout if ctx.join is None else ctx.join.add(K(dout), dout)
+        return dout, dres, None
+
+
+def residual_branch(x):
+    """(x for the branch, join) of a pre-norm residual block ``x + f(x)``: the branch's input
+    gradient and the skip's meet in the join with one ``add_bf16_``, no autograd add."""
+    if torch.is_grad_enabled() and x.requires_grad:
+        join = GradJoin(2)
+        return _JoinInput.apply(x, join), join
+    return x, None
+
+
+def residual_add(y, x, join: Optional[GradJoin] = None):
+    """x + y, written into ``y`` (a fresh branch output, contiguous, same shape)."""
+    if not y.is_contiguous():
+        y = y.contiguous()
+    if torch.is_grad_enabled() and (y.requires_grad or x.requires_grad):
+        if y.is_leaf:
+            y = y.clone()
+        return _ResidualAdd.apply(y, x.contiguous(), join)
+    K(y).add_bf16_(y, x.contiguous())
+    return y
+
+
 # ================================================== BN -> activation -> squeeze-excite gate
 ACT_NONE, ACT_RELU, ACT_HARDSWISH = 0, 1, 2
 

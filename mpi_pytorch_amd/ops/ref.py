@@ -235,6 +235,85 @@ def scale_add_bwd(dout, y, gamma, dgamma, overwrite=False):
     return (_f(dout) * gamma).to(dout.dtype)
 
 
+# ------------------------------------------------ multi-head attention and ViT token kernels
+def _bfr(t):
+    """The bf16 rounding the kernels apply to an MFMA operand, kept in fp32."""
+    return t.to(torch.bfloat16).float()
+
+
+def _attn_qkv(qkv, heads):
+    """q, k, v as [B, H, S, 64] fp32 views of the packed [B, S, 3, H, 64] buffer."""
+    if qkv.dim() == 3 and heads > 0:
+        if qkv.shape[2] != 3 * heads * 64:
+            raise ValueError("attention: last dimension must be 3 * heads * 64")
+        qkv = qkv.reshape(qkv.shape[0], qkv.shape[1], 3, heads, 64)
+    if qkv.dim() != 5 or qkv.shape[2] != 3 or qkv.shape[4] != 64 or not qkv.is_contiguous():
+        raise ValueError("attention: qkv must be contiguous [B, S, 3, H, 64] (head dim 64)")
+    if qkv.shape[1] < 1:
+        raise ValueError("attention: empty sequence")
+    if not qkv.is_floating_point() or qkv.dtype == torch.float64:
+        raise ValueError("attention: qkv must be bf16 (fp32 on the CPU path)")
+    q, k, v = _f(qkv).permute(2, 0, 3, 1, 4)
+    return q, k, v
+
+
+def attn_fwd(qkv, heads=0):
+    """(o [B, S, H 64], lse [B, H, S]): softmax(q k^T / 8) v per head.  Scores, maximum, sum
+    and lse in fp32; P is rounded to bf16 as the P V operand, the row sum uses the unrounded P."""
+    q, k, v = _attn_qkv(qkv, heads)
+    s = (q @ k.transpose(-1, -2)) * 0.125
+    m = s.amax(-1, keepdim=True)
+    p = torch.exp(s - m)
+    l = p.sum(-1, keepdim=True)
+    o = (_bfr(p) @ v) / l
+    B, H, S, _ = q.shape
+    return o.permute(0, 2, 1, 3).reshape(B, S, H * 64).to(qkv.dtype), (m + torch.log(l)).squeeze(-1)
+
+
+def attn_bwd(do, qkv, o, lse, heads=0):
+    """dqkv in qkv's layout: P = exp(s - lse) recomputed, delta = sum_d dO O in fp32,
+    dV = bf16(P)^T dO, dS = P (dO V^T - delta), dQ = bf16(dS) K / 8, dK = bf16(dS)^T Q / 8."""
+    q, k, v = _attn_qkv(qkv, heads)
+    B, H, S, _ = q.shape
+    dof = _f(do).reshape(B, S, H, 64).permute(0, 2, 1, 3)
+    of = _f(o).reshape(B, S, H, 64).permute(0, 2, 1, 3)
+    p = torch.exp((q @ k.transpose(-1, -2)) * 0.125 - lse.unsqueeze(-1))
+    dv = _bfr(p).transpose(-1, -2) @ dof
+    ds = _bfr(p * (dof @ v.transpose(-1, -2) - (dof * of).sum(-1, keepdim=True)))
+    dq = (ds @ k) * 0.125
+    dk = (ds.transpose(-1, -2) @ q) * 0.125
+    return torch.stack([dq, dk, dv]).permute(1, 3, 0, 2, 4).reshape(qkv.shape).contiguous().to(qkv.dtype)
+
+
+def patchify(x, P):
+    """[B Hp Wp, P P C] patch rows (ky, kx, c) of an NHWC image."""
+    B, Hi, Wi, C = x.shape
+    if Hi % P or Wi % P or (P * C) % 8:
+        raise ValueError("patchify: image a multiple of the patch, P * C a multiple of 8")
+    t = x.reshape(B, Hi // P, P, Wi // P, P, C).permute(0, 1, 3, 2, 4, 5)
+    return t.reshape(B * (Hi // P) * (Wi // P), P * P * C).contiguous()
+
+
+def tokens_fwd(patch, cls, pos):
+    """[B, 1 + Np, D]: [cls | patch rows] + pos, fp32 add, one rounding."""
+    D = patch.shape[1]
+    pos = pos.reshape(-1, D)
+    T = pos.shape[0]
+    if D % 8 or T < 2 or patch.shape[0] == 0 or patch.shape[0] % (T - 1):
+        raise ValueError("tokens_fwd: patch rows [B Np, D], pos [1 + Np, D], D a multiple of 8")
+    B = patch.shape[0] // (T - 1)
+    x = torch.cat([cls.reshape(1, 1, D).expand(B, 1, D), _f(patch).reshape(B, T - 1, D)], 1)
+    return (x + pos).to(patch.dtype)
+
+
+def tokens_bwd(dx, dcls, dpos, overwrite=False):
+    B, T, D = dx.shape
+    s = _f(dx).sum(0)
+    _acc(dpos.reshape(T, D), s, overwrite)
+    _acc(dcls.reshape(D), s[0], overwrite)
+    return dx[:, 1:].reshape(B * (T - 1), D).contiguous()
+
+
 # ------------------------------------------------------- squeeze-excite / activation gate
 def _se_t(z, aff):
     """t = aff[0] z + aff[1] as one rounding of the exact value (the kernels' fused
