@@ -746,6 +746,79 @@ Tensor patchify(Tensor x, int64_t P) {
   return rows;
 }
 
+// rows [B (Hi/P) (Wi/P), P P C] -> x [B, Hi, Wi, C]: patchify's inverse (its backward)
+Tensor unpatchify(Tensor rows, int64_t Hi, int64_t Wi, int64_t P) {
+  CHECK_ACT(rows);
+  TORCH_CHECK(rows.dim() == 2 && P > 0 && P < 65536 && Hi > 0 && Wi > 0 && Hi < 65536 && Wi < 65536,
+              "unpatchify: rows must be [B Hp Wp, P P C], P > 0");
+  TORCH_CHECK(rows.numel() > 0 && rows.numel() < ((int64_t)1 << 31), "unpatchify: empty or too large (2^31 elements)");
+  TORCH_CHECK(Hi % P == 0 && Wi % P == 0 && rows.size(1) % (P * P) == 0 &&
+                  rows.size(0) % ((Hi / P) * (Wi / P)) == 0,
+              "unpatchify: rows do not match an image of ", Hi, " x ", Wi, " and patch ", P);
+  const mpa::PatchGeom g{(int)(rows.size(0) / ((Hi / P) * (Wi / P))), (int)Hi, (int)Wi,
+                         (int)(rows.size(1) / (P * P)), (int)P};
+  const char* err = mpa::patch_geom_error(g);
+  TORCH_CHECK(!err, "unpatchify: ", err);
+  TORCH_CHECK(aligned16(rows), "unpatchify: rows must be 16-byte aligned");
+  const c10::OptionalDeviceGuard guard(device_of(rows));
+  Tensor x = empty_like_shape(rows, {g.B, g.Hi, g.Wi, g.Cp}, torch::kBFloat16);
+  mpa::unpatchify(bp(rows), g, bpm(x), cur_stream());
+  return x;
+}
+
+// ------------------------------------------------------ shifted-window attention (wattn.hip)
+// qkv [B Hf Wf, 3 H 32] bf16 contiguous rows in token order, bias H (2 ws - 1)^2 floats.
+// Anything the kernels do not serve is refused here, before an output exists.
+static mpa::WattnGeom wattn_geom(const char* op, const Tensor& qkv, const Tensor& bias, int64_t heads,
+                                 int64_t Hf, int64_t Wf, int64_t ws, int64_t shift) {
+  CHECK_ACT(qkv);
+  TORCH_CHECK(qkv.dim() == 2 && heads > 0 && heads < 65536, op, ": qkv must be [B Hf Wf, 3 H 32] with heads");
+  TORCH_CHECK(Hf > 0 && Wf > 0 && Hf < 65536 && Wf < 65536 && ws > 0 && ws < 65536 && shift >= 0 &&
+                  shift < 65536, op, ": map, window and shift out of range");
+  TORCH_CHECK(qkv.size(1) % (3 * heads) == 0, op, ": last dimension must be 3 * heads * 32, got ",
+              qkv.size(1));
+  TORCH_CHECK(qkv.numel() > 0 && qkv.numel() < ((int64_t)1 << 31), op, ": empty or too large (2^31 elements)");
+  TORCH_CHECK(qkv.size(0) % (Hf * Wf) == 0, op, ": rows must be a multiple of Hf * Wf");
+  const mpa::WattnGeom g{(int)(qkv.size(0) / (Hf * Wf)), (int)heads, (int)Hf, (int)Wf, (int)ws, (int)shift};
+  const char* err = mpa::wattn_geom_error(g, (int)(qkv.size(1) / (3 * heads)));
+  TORCH_CHECK(!err, op, ": ", err);
+  TORCH_CHECK(aligned16(qkv), op, ": qkv must be 16-byte aligned");
+  TORCH_CHECK(bias.defined() && bias.numel() == heads * mpa::wattn_plan(g).nbias, op,
+              ": bias must hold heads * (2 ws - 1)^2 floats");
+  TORCH_CHECK(fopt(bias) != nullptr, op, ": bias must be float32");
+  return g;
+}
+
+std::vector<Tensor> wattn_fwd(Tensor qkv, Tensor bias, int64_t heads, int64_t Hf, int64_t Wf,
+                              int64_t ws, int64_t shift) {
+  const mpa::WattnGeom g = wattn_geom("wattn_fwd", qkv, bias, heads, Hf, Wf, ws, shift);
+  const c10::OptionalDeviceGuard guard(device_of(qkv));
+  Tensor o = empty_like_shape(qkv, {qkv.size(0), (int64_t)g.H * mpa::WA_D}, torch::kBFloat16);
+  Tensor lse = empty_like_shape(qkv, {mpa::wattn_plan(g).nwin, g.H, g.ws * g.ws}, torch::kFloat32);
+  mpa::wattn_fwd(bp(qkv), bias.data_ptr<float>(), g, bpm(o), lse.data_ptr<float>(), cur_stream());
+  return {o, lse};
+}
+
+Tensor wattn_bwd(Tensor d_o, Tensor qkv, Tensor lse, Tensor bias, Tensor dbias, int64_t heads,
+                 int64_t Hf, int64_t Wf, int64_t ws, int64_t shift, bool overwrite) {
+  const mpa::WattnGeom g = wattn_geom("wattn_bwd", qkv, bias, heads, Hf, Wf, ws, shift);
+  const mpa::WattnPlan p = mpa::wattn_plan(g);
+  CHECK_ACT(d_o);
+  TORCH_CHECK(d_o.numel() == qkv.numel() / 3 && aligned16(d_o), "wattn_bwd: do must be [B Hf Wf, H 32]");
+  TORCH_CHECK(has(lse) && lse.numel() == (int64_t)p.nwin * g.H * g.ws * g.ws,
+              "wattn_bwd: lse must be [B nW, H, ws^2]");
+  const float* lp = fopt(lse);
+  TORCH_CHECK(dbias.defined() && dbias.numel() == bias.numel(), "wattn_bwd: dbias must match bias");
+  float* dbp = fopt_mut(dbias);
+  const c10::OptionalDeviceGuard guard(device_of(qkv));
+  Tensor dqkv = torch::empty_like(qkv);
+  Tensor ws_t;
+  float* wsp = alloc_ws(ws_t, qkv, p.ws_floats);
+  mpa::wattn_bwd(bp(d_o), bp(qkv), lp, bias.data_ptr<float>(), g, bpm(dqkv), dbp, overwrite, wsp,
+                 cur_stream());
+  return dqkv;
+}
+
 static const float* tok_vec(const char* op, const char* name, const Tensor& t, int64_t n) {
   TORCH_CHECK(t.defined() && t.numel() == n, op, ": ", name, " must hold ", n, " floats");
   const float* p = fopt(t);
@@ -2569,6 +2642,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "[B, 1 + Np, D]: [cls | patch rows] + pos");
   m.def("tokens_bwd", &tokens_bwd, py::arg("dx"), py::arg("dcls"), py::arg("dpos"),
         py::arg("overwrite") = false, "dpatch = dx[:, 1:]; dcls, dpos (+)= sums over the batch");
+  m.def("unpatchify", &unpatchify, py::arg("rows"), py::arg("Hi"), py::arg("Wi"), py::arg("P"),
+        "the NHWC image [B, Hi, Wi, C] of patch rows: patchify's inverse");
+  m.def("wattn_fwd", &wattn_fwd, py::arg("qkv"), py::arg("bias"), py::arg("heads"), py::arg("Hf"),
+        py::arg("Wf"), py::arg("ws"), py::arg("shift"),
+        "(o, lse): shifted-window attention over the rows qkv [B Hf Wf, 3 H 32] in token order");
+  m.def("wattn_bwd", &wattn_bwd, py::arg("do"), py::arg("qkv"), py::arg("lse"), py::arg("bias"),
+        py::arg("dbias"), py::arg("heads"), py::arg("Hf"), py::arg("Wf"), py::arg("ws"),
+        py::arg("shift"), py::arg("overwrite") = false,
+        "dqkv in qkv's layout; dbias (+)= the relative-position bias gradient");
   m.def("act_pool", &act_pool, py::arg("z"), py::arg("aff"), py::arg("act"),
         "[N, C] mean over H x W of act(aff[0] z + aff[1]) (act 0 identity, 1 ReLU, 2 hardswish)");
   m.def("se_gate", &se_gate, py::arg("pooled"), py::arg("w1"), py::arg("b1"), py::arg("w2"),

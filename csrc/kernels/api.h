@@ -13,6 +13,7 @@
 #include "se_plan.h"
 #include "ln_plan.h"
 #include "attn_plan.h"
+#include "wattn_plan.h"
 
 namespace mpa {
 
@@ -164,6 +165,22 @@ void tokens_fwd(const bf16_raw* patch, const float* cls, const float* pos, const
                 bf16_raw* x, hipStream_t s);
 void tokens_bwd(const bf16_raw* dx, const TokGeom& g, bf16_raw* dpatch, float* dcls, float* dpos,
                 bool overwrite, hipStream_t s);
+// patchify's inverse permutation: x [B][Hi][Wi][Cp] from rows (patchify's backward)
+void unpatchify(const bf16_raw* rows, const PatchGeom& g, bf16_raw* x, hipStream_t s);
+
+// wattn.hip: shifted-window attention over the in-projection's rows qkv [B Hf Wf][3][H][32] bf16
+// in natural token order (wattn_geom_error(g) == nullptr), planned by wattn_plan.h:
+// softmax(q k^T 32^-1/2 + bias[h][rel(i, j)] + mask(i, j)) v per ws x ws window of the map rolled
+// by g.shift; bias [H][(2 ws - 1)^2] fp32.  o [B Hf Wf][H 32] bf16 in token order, lse
+// [B nW][H][ws^2] fp32.  Roll, partition and reverse are address arithmetic; no float atomics.
+void wattn_fwd(const bf16_raw* qkv, const float* bias, const WattnGeom& g, bf16_raw* o, float* lse,
+               hipStream_t s);
+// dqkv has qkv's layout and is written whole; dbias [H][(2 ws - 1)^2] (+)= the bias gradient;
+// ws holds wattn_ws_floats(g) floats
+int64_t wattn_ws_floats(const WattnGeom& g);
+void wattn_bwd(const bf16_raw* d_o, const bf16_raw* qkv, const float* lse, const float* bias,
+               const WattnGeom& g, bf16_raw* dqkv, float* dbias, bool overwrite, float* ws,
+               hipStream_t s);
 
 // se.hip: squeeze-excite and activation-gate kernels, planned by se_plan.h.  z / du / u / dz
 // [N][HW][C] bf16, C % 8 == 0 (se_geom_error(g) == nullptr); t = aff[c] z + aff[C + c] in fp32;

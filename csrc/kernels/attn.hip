@@ -428,6 +428,15 @@ __global__ __launch_bounds__(256) void patchify_kernel(const bf16_t* __restrict_
   st_stream(out + i * 8, ld_stream(x + patch_src(g, i)));
 }
 
+// the inverse permutation: vector i of the rows back to its place in x
+__global__ __launch_bounds__(256) void unpatchify_kernel(const bf16_t* __restrict__ rows,
+                                                         bf16_t* __restrict__ x, PatchGeom g,
+                                                         int64_t nvec) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= nvec) return;
+  st_stream(x + patch_src(g, i), ld_stream(rows + i * 8));
+}
+
 __device__ __forceinline__ void ld8f(const float* p, float* f) {
   const float4 a = *(const float4*)p, b = *(const float4*)(p + 4);
   f[0] = a.x; f[1] = a.y; f[2] = a.z; f[3] = a.w;
@@ -519,6 +528,13 @@ void patchify(const bf16_raw* x, const PatchGeom& g, bf16_raw* rows, hipStream_t
   const int64_t nvec = (int64_t)g.B * g.Hi * g.Wi * g.Cp / 8;
   hipLaunchKernelGGL(patchify_kernel, dim3((unsigned)((nvec + 255) / 256)), dim3(256), 0, s, x,
                      rows, g, nvec);
+  MPA_CHECK_LAUNCH();
+}
+
+void unpatchify(const bf16_raw* rows, const PatchGeom& g, bf16_raw* x, hipStream_t s) {
+  const int64_t nvec = (int64_t)g.B * g.Hi * g.Wi * g.Cp / 8;
+  hipLaunchKernelGGL(unpatchify_kernel, dim3((unsigned)((nvec + 255) / 256)), dim3(256), 0, s,
+                     rows, x, g, nvec);
   MPA_CHECK_LAUNCH();
 }
 

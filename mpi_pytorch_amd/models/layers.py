@@ -493,6 +493,68 @@ class MultiheadAttention(nn.Module):
         return "embed_dim={}, num_heads={}".format(self.embed_dim, self.num_heads)
 
 
+class ShiftedWindowAttention(nn.Module):
+    """Swin's window attention with torchvision's names: ``qkv``, ``proj``,
+    ``relative_position_bias_table`` and the ``relative_position_index`` buffer.  Head dim 32.
+    The in-projection's rows [B Hf Wf, 3 D] are the kernel's input in natural token order and its
+    output rows are the out-projection's input: roll, window partition and reverse are the
+    kernel's address arithmetic, the bias gather and the shift mask its register arithmetic.
+
+    The table is stored flat, head-major [H (2 ws - 1)^2] (1-D: left out of weight decay and
+    trust ratio like ``pos_embedding``), and is [(2 ws - 1)^2, H] in the state_dict.  The int64
+    index buffer exists for state_dict parity only: no kernel reads it."""
+
+    def __init__(self, dim: int, window: int, shift: int, num_heads: int):
+        super().__init__()
+        if dim != 32 * num_heads:
+            raise ValueError("ShiftedWindowAttention: head dim must be 32 (dim = 32 * num_heads)")
+        if window * window > 64 or not 0 <= shift < window:
+            raise ValueError("ShiftedWindowAttention: window^2 <= 64 and 0 <= shift < window")
+        self.dim, self.window, self.shift, self.num_heads = dim, window, shift, num_heads
+        self.qkv = Linear(dim, 3 * dim)
+        self.proj = Linear(dim, dim)
+        nb = (2 * window - 1) ** 2
+        self.relative_position_bias_table = nn.Parameter(
+            nn.init.trunc_normal_(torch.empty(num_heads * nb), std=0.02))
+        self.relative_position_bias_table._mpa_export = self._exp_table
+        self.relative_position_bias_table._mpa_import = self._imp_table
+        self.register_buffer("relative_position_index", Fn.ref.swin_relative_index(window).flatten())
+
+    def _exp_table(self, t):
+        return t.reshape(self.num_heads, -1).t()
+
+    @staticmethod
+    def _imp_table(t):
+        return t.t().reshape(-1)
+
+    def _save_to_state_dict(self, destination, prefix, keep_vars):
+        super()._save_to_state_dict(destination, prefix, keep_vars)
+        k = prefix + "relative_position_bias_table"
+        if k in destination:
+            t = self._exp_table(destination[k])
+            destination[k] = t if keep_vars else t.contiguous()
+
+    def _load_from_state_dict(self, state_dict, prefix, *args, **kwargs):
+        k = prefix + "relative_position_bias_table"
+        if k in state_dict and state_dict[k].dim() == 2:
+            state_dict[k] = self._imp_table(state_dict[k])
+        super()._load_from_state_dict(state_dict, prefix, *args, **kwargs)
+
+    def forward(self, rows, Hf: int, Wf: int):
+        """rows [B Hf Wf, D] -> [B Hf Wf, D]"""
+        shift = 0 if min(Hf, Wf) <= self.window else self.shift  # one window: nothing to shift
+        qkv = Fn.linear_act(rows, self.qkv)
+        if not qkv.is_contiguous():
+            qkv = qkv.contiguous()
+        o = Fn.window_attention(qkv, self.relative_position_bias_table, self.num_heads, Hf, Wf,
+                                self.window, shift)
+        return Fn.linear_act(o, self.proj)
+
+    def extra_repr(self):
+        return "dim={}, window={}, shift={}, num_heads={}".format(self.dim, self.window, self.shift,
+                                                                  self.num_heads)
+
+
 class PatchEmbed(nn.Module):
     """ViT's patch embedding, a P x P / stride P conv, as patch rows times a [D, P P Cp] matrix
     (``Fn.patch_tokens``).  The state_dict holds torchvision's ``weight`` [D, C, P, P] and

@@ -1189,6 +1189,57 @@ def patch_tokens(x, embed, cls, pos):
     return K(pr).tokens_fwd(pr, cls, pos)
 
 
+# ======================================= shifted-window attention and patch merging (Swin)
+class _WindowAttention(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, qkv, bias, heads, Hf, Wf, ws, shift):
+        o, lse = K(qkv).wattn_fwd(qkv, bias, heads, Hf, Wf, ws, shift)
+        ctx.bias, ctx.geom = bias, (heads, Hf, Wf, ws, shift)
+        ctx.save_for_backward(qkv, lse)
+        return o
+
+    @staticmethod
+    def backward(ctx, do):
+        qkv, lse = ctx.saved_tensors
+        bias, k = ctx.bias, K(do)
+        do = do.contiguous()
+        if not bias.requires_grad:  # frozen: the bias gradient into scratch
+            tmp = torch.empty(bias.numel(), device=do.device, dtype=torch.float32)
+            return _grads(_WindowAttention, k.wattn_bwd(do, qkv, lse, bias, tmp, *ctx.geom, True))
+        dqkv = k.wattn_bwd(do, qkv, lse, bias, grad_sink(bias), *ctx.geom, _fresh(bias))
+        _done(bias)
+        return _grads(_WindowAttention, dqkv)
+
+
+def window_attention(qkv, bias, heads: int, Hf: int, Wf: int, ws: int, shift: int):
+    """Swin's attention over the in-projection's rows ``qkv`` [B Hf Wf, 3 * heads * 32] in natural
+    token order: softmax(q k^T / sqrt(32) + bias[h][rel] + shift mask) v inside every ws x ws
+    window of the map rolled by ``shift``; ``bias`` holds heads * (2 ws - 1)^2 floats.  Returns
+    rows [B Hf Wf, heads * 32] in the same order: no roll, partition or reverse pass exists."""
+    if torch.is_grad_enabled() and (qkv.requires_grad or bias.requires_grad):
+        return _WindowAttention.apply(qkv, bias, heads, Hf, Wf, ws, shift)
+    return K(qkv).wattn_fwd(qkv, bias, heads, Hf, Wf, ws, shift)[0]
+
+
+class _PatchMerge(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x):
+        ctx.hw = (x.shape[1], x.shape[2])
+        return K(x).patchify(x, 2)
+
+    @staticmethod
+    def backward(ctx, drows):
+        return K(drows).unpatchify(drows.contiguous(), ctx.hw[0], ctx.hw[1], 2)
+
+
+def patch_merge_rows(x):
+    """Swin's patch merging gather: NHWC [B, Hf, Wf, C] -> rows [B Hf/2 Wf/2, 4 C], each 2 x 2 cell
+    in (ky, kx, c) order (``patchify`` forward, ``unpatchify`` backward)."""
+    if torch.is_grad_enabled() and x.requires_grad:
+        return _PatchMerge.apply(x)
+    return K(x).patchify(x, 2)
+
+
 class _JoinInput(torch.autograd.Function):
     """Identity in front of one consumer of an activation whose gradient contributions meet in
     ``join``: its backward hands the consumer's gradient in."""

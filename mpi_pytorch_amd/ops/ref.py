@@ -294,6 +294,122 @@ def patchify(x, P):
     return t.reshape(B * (Hi // P) * (Wi // P), P * P * C).contiguous()
 
 
+def unpatchify(rows, Hi, Wi, P):
+    """patchify's inverse: the NHWC image [B, Hi, Wi, C] of patch rows [B Hp Wp, P P C]."""
+    if rows.dim() != 2 or Hi % P or Wi % P or rows.shape[1] % (P * P):
+        raise ValueError("unpatchify: rows [B Hp Wp, P P C] of an image a multiple of the patch")
+    C, npatch = rows.shape[1] // (P * P), (Hi // P) * (Wi // P)
+    if rows.shape[0] % npatch or (P * C) % 8:
+        raise ValueError("unpatchify: rows do not match the image, or P * C is no multiple of 8")
+    t = rows.reshape(rows.shape[0] // npatch, Hi // P, Wi // P, P, P, C).permute(0, 1, 3, 2, 4, 5)
+    return t.reshape(-1, Hi, Wi, C).contiguous()
+
+
+# ---------------------------------------------------------- shifted-window attention (Swin)
+# Written the textbook way (roll, reshape / permute partition, an index table, a mask tensor
+# from the slice loops of the published algorithm): the kernels' closed-form addressing is
+# checked against an independent formulation.
+WATTN_SCALE = 0.17677669529663687  # 32^-1/2 (one fp32 rounding where it multiplies fp32)
+
+
+def window_partition(t, Hf, Wf, ws, shift):
+    """rows [B Hf Wf, C] -> windows [B nW, ws^2, C] of the map rolled by -shift."""
+    C = t.shape[-1]
+    x = t.reshape(-1, Hf, Wf, C)
+    if shift:
+        x = torch.roll(x, shifts=(-shift, -shift), dims=(1, 2))
+    x = x.reshape(x.shape[0], Hf // ws, ws, Wf // ws, ws, C).permute(0, 1, 3, 2, 4, 5)
+    return x.reshape(-1, ws * ws, C)
+
+
+def window_reverse(w, Hf, Wf, ws, shift):
+    """window_partition's inverse: [B nW, ws^2, C] -> rows [B Hf Wf, C]."""
+    C = w.shape[-1]
+    x = w.reshape(-1, Hf // ws, Wf // ws, ws, ws, C).permute(0, 1, 3, 2, 4, 5).reshape(-1, Hf, Wf, C)
+    if shift:
+        x = torch.roll(x, shifts=(shift, shift), dims=(1, 2))
+    return x.reshape(-1, C)
+
+
+def swin_relative_index(ws):
+    """[ws^2, ws^2] int64 index into a head's (2 ws - 1)^2 bias row (torchvision's buffer)."""
+    c = torch.stack(torch.meshgrid(torch.arange(ws), torch.arange(ws), indexing="ij")).flatten(1)
+    rel = (c[:, :, None] - c[:, None, :]).permute(1, 2, 0).contiguous()
+    rel[:, :, 0] += ws - 1
+    rel[:, :, 1] += ws - 1
+    rel[:, :, 0] *= 2 * ws - 1
+    return rel.sum(-1)
+
+
+def swin_shift_mask(Hf, Wf, ws, shift):
+    """[nW, ws^2, ws^2] fp32: -100 where two tokens of a window lie in different regions of the
+    rolled map, else 0 (all zero without a shift)."""
+    m = torch.zeros(Hf, Wf)
+    if shift:
+        count = 0
+        for h in ((0, -ws), (-ws, -shift), (-shift, None)):
+            for w in ((0, -ws), (-ws, -shift), (-shift, None)):
+                m[h[0]:h[1], w[0]:w[1]] = count
+                count += 1
+    m = m.reshape(Hf // ws, ws, Wf // ws, ws).permute(0, 2, 1, 3).reshape(-1, ws * ws)
+    d = m[:, None, :] - m[:, :, None]
+    return torch.where(d != 0, torch.full_like(d, -100.0), torch.zeros_like(d))
+
+
+def _wattn_operands(qkv, bias, heads, Hf, Wf, ws, shift):
+    """q, k, v [B nW, H, ws^2, 32] fp32 and the additive term [B nW, H, ws^2, ws^2]."""
+    if qkv.dim() != 2 or heads < 1 or not qkv.is_contiguous():
+        raise ValueError("window attention: qkv must be contiguous rows [B Hf Wf, 3 H 32]")
+    if not qkv.is_floating_point() or qkv.dtype == torch.float64 or bias.dtype != torch.float32:
+        raise ValueError("window attention: qkv must be bf16 (fp32 on the CPU path), bias fp32")
+    if qkv.shape[1] != 3 * heads * 32:
+        raise ValueError("window attention: head dim must be 32")
+    if ws < 1 or ws * ws > 64 or Hf % ws or Wf % ws or not 0 <= shift < ws:
+        raise ValueError("window attention: ws^2 <= 64, map a multiple of ws, 0 <= shift < ws")
+    if qkv.shape[0] == 0 or qkv.shape[0] % (Hf * Wf) or bias.numel() != heads * (2 * ws - 1) ** 2:
+        raise ValueError("window attention: rows a multiple of Hf Wf, bias H (2 ws - 1)^2 floats")
+    S2 = ws * ws
+    w = window_partition(_f(qkv), Hf, Wf, ws, shift)
+    q, k, v = w.reshape(-1, S2, 3, heads, 32).permute(2, 0, 3, 1, 4)
+    idx = swin_relative_index(ws).reshape(-1).to(qkv.device)
+    add = bias.reshape(heads, -1)[:, idx].reshape(1, heads, S2, S2)
+    mask = swin_shift_mask(Hf, Wf, ws, shift).to(qkv.device)
+    mask = mask.repeat(w.shape[0] // mask.shape[0], 1, 1)[:, None]
+    return q, k, v, add, mask, idx
+
+
+def wattn_fwd(qkv, bias, heads, Hf, Wf, ws, shift):
+    """(o [B Hf Wf, H 32], lse [B nW, H, ws^2]): softmax(q k^T 32^-1/2 + bias + mask) v per window
+    of the rolled map; fp32 scores and statistics, P a bf16 operand, the row sum unrounded."""
+    q, k, v, add, mask, _ = _wattn_operands(qkv, bias, heads, Hf, Wf, ws, shift)
+    s = (q @ k.transpose(-1, -2)) * WATTN_SCALE + add + mask
+    m = s.amax(-1, keepdim=True)
+    p = torch.exp(s - m)
+    l = p.sum(-1, keepdim=True)
+    o = ((_bfr(p) @ v) / l).permute(0, 2, 1, 3).reshape(-1, ws * ws, heads * 32)
+    return window_reverse(o, Hf, Wf, ws, shift).to(qkv.dtype), (m + torch.log(l)).squeeze(-1)
+
+
+def wattn_bwd(do, qkv, lse, bias, dbias, heads, Hf, Wf, ws, shift, overwrite=False):
+    """dqkv in qkv's layout, dbias (+)= the fp32 sum of the unrounded dS over the entries of each
+    relative index: P = exp(s - lse), delta = sum_j P dP, dS = P (dP - delta), dV = bf16(P)^T dO,
+    dQ = bf16(dS) K 32^-1/2, dK = bf16(dS)^T Q 32^-1/2."""
+    q, k, v, add, mask, idx = _wattn_operands(qkv, bias, heads, Hf, Wf, ws, shift)
+    S2 = ws * ws
+    dof = window_partition(_f(do), Hf, Wf, ws, shift).reshape(-1, S2, heads, 32).permute(0, 2, 1, 3)
+    p = torch.exp((q @ k.transpose(-1, -2)) * WATTN_SCALE + add + mask - lse.unsqueeze(-1))
+    dp = dof @ v.transpose(-1, -2)
+    ds = p * (dp - (p * dp).sum(-1, keepdim=True))
+    dv = _bfr(p).transpose(-1, -2) @ dof
+    dq = (_bfr(ds) @ k) * WATTN_SCALE
+    dk = (_bfr(ds).transpose(-1, -2) @ q) * WATTN_SCALE
+    db = torch.zeros(heads, (2 * ws - 1) ** 2, device=qkv.device)
+    db.index_add_(1, idx, ds.sum(0).reshape(heads, S2 * S2))
+    _acc(dbias.reshape(heads, -1), db, overwrite)
+    w = torch.stack([dq, dk, dv]).permute(1, 3, 0, 2, 4).reshape(-1, S2, 3 * heads * 32)
+    return window_reverse(w, Hf, Wf, ws, shift).contiguous().to(qkv.dtype)
+
+
 def tokens_fwd(patch, cls, pos):
     """[B, 1 + Np, D]: [cls | patch rows] + pos, fp32 add, one rounding."""
     D = patch.shape[1]
