@@ -819,6 +819,89 @@ Tensor wattn_bwd(Tensor d_o, Tensor qkv, Tensor lse, Tensor bias, Tensor dbias, 
   return dqkv;
 }
 
+// the cosine variant (Swin V2): wattn_geom's refusals, and logit_scale must be [H] float32
+static const float* wattn_logit(const char* op, const Tensor& logit_scale, int64_t heads) {
+  TORCH_CHECK(logit_scale.defined() && logit_scale.numel() == heads, op, ": logit_scale must hold heads floats");
+  const float* p = fopt(logit_scale);
+  TORCH_CHECK(p != nullptr, op, ": logit_scale must be float32");
+  return p;
+}
+
+std::vector<Tensor> wattn_cos_fwd(Tensor qkv, Tensor logit_scale, Tensor bias, int64_t heads, int64_t Hf,
+                                  int64_t Wf, int64_t ws, int64_t shift) {
+  const mpa::WattnGeom g = wattn_geom("wattn_cos_fwd", qkv, bias, heads, Hf, Wf, ws, shift);
+  const float* lp = wattn_logit("wattn_cos_fwd", logit_scale, heads);
+  const c10::OptionalDeviceGuard guard(device_of(qkv));
+  Tensor o = empty_like_shape(qkv, {qkv.size(0), (int64_t)g.H * mpa::WA_D}, torch::kBFloat16);
+  Tensor lse = empty_like_shape(qkv, {mpa::wattn_plan(g, true).nwin, g.H, g.ws * g.ws}, torch::kFloat32);
+  mpa::wattn_cos_fwd(bp(qkv), lp, bias.data_ptr<float>(), g, bpm(o), lse.data_ptr<float>(), cur_stream());
+  return {o, lse};
+}
+
+Tensor wattn_cos_bwd(Tensor d_o, Tensor qkv, Tensor lse, Tensor logit_scale, Tensor bias, Tensor dbias,
+                     Tensor dlogit, int64_t heads, int64_t Hf, int64_t Wf, int64_t ws, int64_t shift,
+                     bool overwrite) {
+  const mpa::WattnGeom g = wattn_geom("wattn_cos_bwd", qkv, bias, heads, Hf, Wf, ws, shift);
+  const mpa::WattnPlan p = mpa::wattn_plan(g, true);
+  const float* sp = wattn_logit("wattn_cos_bwd", logit_scale, heads);
+  CHECK_ACT(d_o);
+  TORCH_CHECK(d_o.numel() == qkv.numel() / 3 && aligned16(d_o), "wattn_cos_bwd: do must be [B Hf Wf, H 32]");
+  TORCH_CHECK(has(lse) && lse.numel() == (int64_t)p.nwin * g.H * g.ws * g.ws,
+              "wattn_cos_bwd: lse must be [B nW, H, ws^2]");
+  const float* lp = fopt(lse);
+  TORCH_CHECK(dbias.defined() && dbias.numel() == bias.numel(), "wattn_cos_bwd: dbias must match bias");
+  TORCH_CHECK(dlogit.defined() && dlogit.numel() == heads, "wattn_cos_bwd: dlogit must match logit_scale");
+  float* dbp = fopt_mut(dbias);
+  float* dlp = fopt_mut(dlogit);
+  const c10::OptionalDeviceGuard guard(device_of(qkv));
+  Tensor dqkv = torch::empty_like(qkv);
+  Tensor ws_t;
+  float* wsp = alloc_ws(ws_t, qkv, p.ws_floats);
+  mpa::wattn_cos_bwd(bp(d_o), bp(qkv), lp, sp, bias.data_ptr<float>(), g, bpm(dqkv), dbp, dlp, overwrite,
+                     wsp, cur_stream());
+  return dqkv;
+}
+
+// ------------------------------------------------- continuous position bias (cpb.hip), all fp32
+static int64_t cpb_check(const char* op, const Tensor& w1, const Tensor& b1, const Tensor& w2,
+                         int64_t heads, int64_t ws) {
+  TORCH_CHECK(heads > 0 && heads < 65536 && ws >= 2 && ws * ws <= mpa::WA_N, op,
+              ": heads > 0 and a window of 2 <= ws, ws^2 <= 64");
+  TORCH_CHECK(w1.defined() && w1.dim() == 2 && w1.size(0) == mpa::CPB_HIDDEN && w1.size(1) == 2, op,
+              ": w1 must be [512, 2]");
+  TORCH_CHECK(b1.defined() && b1.numel() == mpa::CPB_HIDDEN, op, ": b1 must hold 512 floats");
+  TORCH_CHECK(w2.defined() && w2.dim() == 2 && w2.size(0) == heads && w2.size(1) == mpa::CPB_HIDDEN, op,
+              ": w2 must be [heads, 512]");
+  TORCH_CHECK(fopt(w1) && fopt(b1) && fopt(w2), op, ": w1, b1 and w2 must be float32");
+  return heads * (2 * ws - 1) * (2 * ws - 1);
+}
+
+Tensor cpb_fwd(Tensor w1, Tensor b1, Tensor w2, int64_t heads, int64_t ws) {
+  const int64_t n = cpb_check("cpb_fwd", w1, b1, w2, heads, ws);
+  const c10::OptionalDeviceGuard guard(device_of(w1));
+  Tensor bias = empty_like_shape(w1, {n}, torch::kFloat32);
+  mpa::cpb_fwd(fopt(w1), fopt(b1), fopt(w2), (int)heads, (int)ws, bias.data_ptr<float>(), cur_stream());
+  return bias;
+}
+
+void cpb_bwd(Tensor dbias, Tensor bias, Tensor w1, Tensor b1, Tensor w2, Tensor dw1, Tensor db1,
+             Tensor dw2, int64_t heads, int64_t ws, bool overwrite) {
+  const int64_t n = cpb_check("cpb_bwd", w1, b1, w2, heads, ws);
+  TORCH_CHECK(dbias.defined() && bias.defined() && dbias.numel() == n && bias.numel() == n,
+              "cpb_bwd: dbias and bias must hold heads * (2 ws - 1)^2 floats");
+  TORCH_CHECK(dw1.defined() && db1.defined() && dw2.defined() && dw1.numel() == w1.numel() &&
+                  db1.numel() == b1.numel() && dw2.numel() == w2.numel(),
+              "cpb_bwd: dw1, db1 and dw2 must match w1, b1 and w2");
+  const float* dbp = fopt(dbias);
+  const float* bp_ = fopt(bias);
+  float* g1 = fopt_mut(dw1);
+  float* gb = fopt_mut(db1);
+  float* g2 = fopt_mut(dw2);
+  const c10::OptionalDeviceGuard guard(device_of(w1));
+  mpa::cpb_bwd(dbp, bp_, fopt(w1), fopt(b1), fopt(w2), (int)heads, (int)ws, g1, gb, g2, overwrite,
+               cur_stream());
+}
+
 static const float* tok_vec(const char* op, const char* name, const Tensor& t, int64_t n) {
   TORCH_CHECK(t.defined() && t.numel() == n, op, ": ", name, " must hold ", n, " floats");
   const float* p = fopt(t);
@@ -2651,6 +2734,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("dbias"), py::arg("heads"), py::arg("Hf"), py::arg("Wf"), py::arg("ws"),
         py::arg("shift"), py::arg("overwrite") = false,
         "dqkv in qkv's layout; dbias (+)= the relative-position bias gradient");
+  m.def("wattn_cos_fwd", &wattn_cos_fwd, py::arg("qkv"), py::arg("logit_scale"), py::arg("bias"),
+        py::arg("heads"), py::arg("Hf"), py::arg("Wf"), py::arg("ws"), py::arg("shift"),
+        "(o, lse): Swin V2's cosine window attention, temperature exp(min(logit_scale, ln 100))");
+  m.def("wattn_cos_bwd", &wattn_cos_bwd, py::arg("do"), py::arg("qkv"), py::arg("lse"),
+        py::arg("logit_scale"), py::arg("bias"), py::arg("dbias"), py::arg("dlogit"), py::arg("heads"),
+        py::arg("Hf"), py::arg("Wf"), py::arg("ws"), py::arg("shift"), py::arg("overwrite") = false,
+        "dqkv in qkv's layout; dbias, dlogit (+)= the bias and logit-scale gradients");
+  m.def("cpb_fwd", &cpb_fwd, py::arg("w1"), py::arg("b1"), py::arg("w2"), py::arg("heads"), py::arg("ws"),
+        "[H (2 ws - 1)^2] fp32: 16 sigmoid(w2 relu(w1 coord + b1)) over the log-spaced offsets");
+  m.def("cpb_bwd", &cpb_bwd, py::arg("dbias"), py::arg("bias"), py::arg("w1"), py::arg("b1"),
+        py::arg("w2"), py::arg("dw1"), py::arg("db1"), py::arg("dw2"), py::arg("heads"), py::arg("ws"),
+        py::arg("overwrite") = false, "dw1, db1, dw2 (+)= the position-bias MLP's gradients");
   m.def("act_pool", &act_pool, py::arg("z"), py::arg("aff"), py::arg("act"),
         "[N, C] mean over H x W of act(aff[0] z + aff[1]) (act 0 identity, 1 ReLU, 2 hardswish)");
   m.def("se_gate", &se_gate, py::arg("pooled"), py::arg("w1"), py::arg("b1"), py::arg("w2"),

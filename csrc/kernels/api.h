@@ -181,6 +181,27 @@ int64_t wattn_ws_floats(const WattnGeom& g);
 void wattn_bwd(const bf16_raw* d_o, const bf16_raw* qkv, const float* lse, const float* bias,
                const WattnGeom& g, bf16_raw* dqkv, float* dbias, bool overwrite, float* ws,
                hipStream_t s);
+// the cosine variant (Swin V2), same geometry, layouts and plan (wattn_plan(g, true)):
+// softmax(tau_h (q^ . k^) + bias + mask) v with q^ = q / max(|q|, 1e-12), the same for k, and
+// tau_h = exp(min(logit_scale[h], ln 100)); logit_scale [H] fp32
+void wattn_cos_fwd(const bf16_raw* qkv, const float* logit_scale, const float* bias,
+                   const WattnGeom& g, bf16_raw* o, float* lse, hipStream_t s);
+// dlogit [H] (+)= the logit-scale gradient (0 for a clamped head) under dbias's overwrite flag;
+// ws holds wattn_cos_ws_floats(g) floats
+int64_t wattn_cos_ws_floats(const WattnGeom& g);
+void wattn_cos_bwd(const bf16_raw* d_o, const bf16_raw* qkv, const float* lse, const float* logit_scale,
+                   const float* bias, const WattnGeom& g, bf16_raw* dqkv, float* dbias, float* dlogit,
+                   bool overwrite, float* ws, hipStream_t s);
+
+// cpb.hip: Swin V2's continuous position bias, all fp32.  bias [H][(2 ws - 1)^2] =
+// 16 sigmoid(w2 relu(w1 coord + b1)) over the log-spaced relative coordinates of a ws x ws window
+// (2 <= ws), w1 [CPB_HIDDEN][2], b1 [CPB_HIDDEN], w2 [H][CPB_HIDDEN]: the table wattn_cos_fwd reads
+constexpr int CPB_HIDDEN = 512;
+void cpb_fwd(const float* w1, const float* b1, const float* w2, int H, int ws, float* bias,
+             hipStream_t s);
+// dw1, db1, dw2 (+)= the MLP's gradients from dbias and the stored table; no atomics
+void cpb_bwd(const float* dbias, const float* bias, const float* w1, const float* b1, const float* w2,
+             int H, int ws, float* dw1, float* db1, float* dw2, bool overwrite, hipStream_t s);
 
 // se.hip: squeeze-excite and activation-gate kernels, planned by se_plan.h.  z / du / u / dz
 // [N][HW][C] bf16, C % 8 == 0 (se_geom_error(g) == nullptr); t = aff[c] z + aff[C + c] in fp32;

@@ -22,6 +22,9 @@
 //   backward  Kt 4608 | Qt 4608 | dOt 4608 | bias row 1024 | rows 256 | info 256 | lse 256 |
 //             delta 256;   phase A's dQ patch lies in dOt (staged after phase A), phase B's dK
 //             and dV patches and the bias-gradient fold (16 x 65 floats) lie in Kt.
+//   cosine variant (wattn_cos_*): the rows' inverse norms follow, rk 256 in the forward (a
+//             lane keeps its queries' in registers), rq 256 | rk 256 in the backward, whose
+//             slab row gains one column per head, the temperature gradient.
 #pragma once
 #include <stdint.h>
 
@@ -38,6 +41,9 @@ constexpr int WA_BIAS_MAX = 256;  // floats of a head's bias row in LDS: (2 * 8 
 constexpr int WA_FOLD_PITCH = 65; // floats per query row of the fold's [16][64] dS slice
 constexpr int WA_FWD_BYTES = WA_TILE_BYTES + 16 * WA_PPITCH * 2 + WA_BIAS_MAX * 4 + 2 * WA_N * 4;
 constexpr int WA_BWD_BYTES = 3 * WA_TILE_BYTES + WA_BIAS_MAX * 4 + 4 * WA_N * 4;
+constexpr int WA_NORM_BYTES = WA_N * 4;  // cosine variant: the inverse norms of one operand's rows
+constexpr int WA_FWD_COS_BYTES = WA_FWD_BYTES + WA_NORM_BYTES;
+constexpr int WA_BWD_COS_BYTES = WA_BWD_BYTES + 2 * WA_NORM_BYTES;
 constexpr int WA_FILL_BLOCKS = 512;  // two 4-wave blocks per CU before the walks lengthen
 constexpr int WA_MAX_ROWS = 512;     // slab rows (per head group) are capped here
 
@@ -52,8 +58,9 @@ struct WattnPlan {
   int wpb;           // windows a backward block walks
   int rows;          // slab rows = backward grid.x = ceil(nwin / wpb)
   int nbias;         // (2 ws - 1)^2
+  int slab_cols;     // floats per head of a slab row: nbias, + 1 (temperature) in the cosine variant
   int lds_fwd, lds_bwd;  // static LDS bytes per block
-  int64_t ws_floats;     // slab floats: rows * H * nbias
+  int64_t ws_floats;     // slab floats: rows * H * slab_cols
 };
 
 // head_dim is the width of one head in qkv's columns (columns / (3 H))
@@ -68,7 +75,8 @@ inline const char* wattn_geom_error(const WattnGeom& g, int head_dim = WA_D) {
   return nullptr;
 }
 
-inline WattnPlan wattn_plan(const WattnGeom& g) {
+// cosine: the plan of wattn_cos_fwd / wattn_cos_bwd (same grid, larger LDS and slab rows)
+inline WattnPlan wattn_plan(const WattnGeom& g, bool cosine = false) {
   WattnPlan p{};
   p.waves = g.H % 4 == 0 ? 4 : g.H % 3 == 0 ? 3 : g.H % 2 == 0 ? 2 : 1;
   p.groups = g.H / p.waves;
@@ -81,9 +89,10 @@ inline WattnPlan wattn_plan(const WattnGeom& g) {
   p.wpb = (p.nwin + rows - 1) / rows;
   p.rows = (p.nwin + p.wpb - 1) / p.wpb;
   p.nbias = (2 * g.ws - 1) * (2 * g.ws - 1);
-  p.lds_fwd = p.waves * WA_FWD_BYTES;
-  p.lds_bwd = p.waves * WA_BWD_BYTES;
-  p.ws_floats = (int64_t)p.rows * g.H * p.nbias;
+  p.slab_cols = p.nbias + (cosine ? 1 : 0);
+  p.lds_fwd = p.waves * (cosine ? WA_FWD_COS_BYTES : WA_FWD_BYTES);
+  p.lds_bwd = p.waves * (cosine ? WA_BWD_COS_BYTES : WA_BWD_BYTES);
+  p.ws_floats = (int64_t)p.rows * g.H * p.slab_cols;
   return p;
 }
 

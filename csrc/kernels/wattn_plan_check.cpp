@@ -31,6 +31,13 @@ static void check_geom(const WattnGeom& g) {
   REQUIRE(p.ws_floats == (int64_t)p.rows * g.H * p.nbias);
   REQUIRE(p.lds_fwd == p.waves * WA_FWD_BYTES && p.lds_bwd == p.waves * WA_BWD_BYTES);
   REQUIRE(p.lds_fwd <= AT_LDS_LIMIT && p.lds_bwd <= AT_LDS_LIMIT);
+  // the cosine variant: the same grid and walks, two norm rows more LDS, one slab column more
+  const WattnPlan c = wattn_plan(g, true);
+  REQUIRE(c.waves == p.waves && c.groups == p.groups && c.nwin == p.nwin && c.wpb == p.wpb && c.rows == p.rows);
+  REQUIRE(c.nbias == p.nbias && p.slab_cols == p.nbias && c.slab_cols == p.nbias + 1);
+  REQUIRE(c.ws_floats == (int64_t)c.rows * g.H * c.slab_cols);
+  REQUIRE(c.lds_fwd == p.waves * WA_FWD_COS_BYTES && c.lds_bwd == p.waves * WA_BWD_COS_BYTES);
+  REQUIRE(c.lds_fwd <= AT_LDS_LIMIT && c.lds_bwd <= AT_LDS_LIMIT);
 
   // a labelled map, rolled by brute force: label[pixel] = region of the pixel's rolled position
   std::vector<int> rolled_region(npix, -1);
@@ -69,6 +76,8 @@ int main() {
   REQUIRE(WA_PITCH % 8 == 0 && WA_PITCH >= WA_N + 8 && WA_PPITCH % 8 == 0 && WA_PPITCH >= WA_D);
   REQUIRE(WA_FWD_BYTES % 16 == 0 && WA_BWD_BYTES % 16 == 0 && WA_TILE_BYTES % 16 == 0);
   REQUIRE(4 * WA_BWD_BYTES <= AT_LDS_LIMIT && 4 * WA_FWD_BYTES <= AT_LDS_LIMIT);
+  REQUIRE(WA_FWD_COS_BYTES % 16 == 0 && WA_BWD_COS_BYTES % 16 == 0 && WA_NORM_BYTES == WA_N * 4);
+  REQUIRE(4 * WA_BWD_COS_BYTES <= AT_LDS_LIMIT && 4 * WA_FWD_COS_BYTES <= AT_LDS_LIMIT);
   REQUIRE(16 * WA_PPITCH * 2 <= WA_TILE_BYTES);            // phase A's dQ patch in dOt
   REQUIRE(2 * 16 * WA_PPITCH * 2 <= WA_TILE_BYTES);        // phase B's dK and dV patches in Kt
   REQUIRE(16 * WA_FOLD_PITCH * 4 <= WA_TILE_BYTES && WA_FOLD_PITCH >= WA_N);  // the fold in Kt

@@ -555,6 +555,94 @@ class ShiftedWindowAttention(nn.Module):
                                                                   self.num_heads)
 
 
+class _MlpLayer(nn.Module):
+    """``weight`` [out, in] and ``bias`` of one layer of the position-bias MLP, stored as they
+    are (fp32, no pad rows): ``Fn.cpb_bias`` reads both layers in one kernel."""
+
+    def __init__(self, in_features: int, out_features: int, bias: bool):
+        super().__init__()
+        self.weight = nn.Parameter(nn.init.trunc_normal_(torch.empty(out_features, in_features), std=0.02))
+        self.bias = nn.Parameter(torch.zeros(out_features)) if bias else None
+
+
+class ShiftedWindowAttentionV2(nn.Module):
+    """Swin V2's window attention with torchvision's names: ``qkv``, ``proj``, ``logit_scale``,
+    ``cpb_mlp.0.weight / bias``, ``cpb_mlp.2.weight`` and the ``relative_coords_table`` and
+    ``relative_position_index`` buffers.  Head dim 32.  Scores are cosines times the clamped
+    temperature exp(min(logit_scale, ln 100)) plus 16 sigmoid(cpb_mlp(log-spaced offsets)):
+    ``Fn.cpb_bias`` writes the table in fp32, ``Fn.window_attention_cos`` reads the
+    in-projection's rows in natural token order and normalises inside the score tile.
+
+    ``logit_scale`` is stored flat [H] (1-D: left out of weight decay and trust ratio) and is
+    [H, 1, 1] in the state_dict.  The k third of the qkv bias is treated as zero, as torchvision
+    does in its forward: it is zero at construction and on import, and its gradient is cleared
+    in the in-projection's backward, so it stays zero.  The two buffers exist for state_dict
+    parity only: no kernel reads them."""
+
+    def __init__(self, dim: int, window: int, shift: int, num_heads: int):
+        super().__init__()
+        if dim != 32 * num_heads:
+            raise ValueError("ShiftedWindowAttentionV2: head dim must be 32 (dim = 32 * num_heads)")
+        if window < 2 or window * window > 64 or not 0 <= shift < window:
+            raise ValueError("ShiftedWindowAttentionV2: 2 <= window, window^2 <= 64, 0 <= shift < window")
+        self.dim, self.window, self.shift, self.num_heads = dim, window, shift, num_heads
+        self.qkv = Linear(dim, 3 * dim)
+        self.proj = Linear(dim, dim)
+        self._zero_k_bias()
+        self.logit_scale = nn.Parameter(torch.full((num_heads,), math.log(10.0)))
+        self.logit_scale._mpa_export = self._exp_scale
+        self.logit_scale._mpa_import = self._imp_scale
+        self.cpb_mlp = nn.Sequential(_MlpLayer(2, 512, True), nn.Identity(), _MlpLayer(512, num_heads, False))
+        c = torch.arange(-(window - 1), window, dtype=torch.float32)
+        t = torch.stack(torch.meshgrid([c, c], indexing="ij")).permute(1, 2, 0).contiguous().unsqueeze(0)
+        t = t / (window - 1) * 8
+        self.register_buffer("relative_coords_table", torch.sign(t) * torch.log2(t.abs() + 1.0) / 3.0)
+        self.register_buffer("relative_position_index", Fn.ref.swin_relative_index(window).flatten())
+
+    @staticmethod
+    def _exp_scale(t):
+        return t.reshape(-1, 1, 1)
+
+    @staticmethod
+    def _imp_scale(t):
+        return t.reshape(-1)
+
+    def _save_to_state_dict(self, destination, prefix, keep_vars):
+        super()._save_to_state_dict(destination, prefix, keep_vars)
+        k = prefix + "logit_scale"
+        if k in destination:
+            destination[k] = self._exp_scale(destination[k])
+
+    def _load_from_state_dict(self, state_dict, prefix, *args, **kwargs):
+        k = prefix + "logit_scale"
+        if k in state_dict and state_dict[k].dim() == 3:
+            state_dict[k] = self._imp_scale(state_dict[k])
+        k = prefix + "qkv.bias"
+        if k in state_dict:  # (the child module loads it after this hook)
+            state_dict[k] = state_dict[k].clone()
+            state_dict[k][self.dim:2 * self.dim] = 0
+        super()._load_from_state_dict(state_dict, prefix, *args, **kwargs)
+
+    def _zero_k_bias(self):
+        with torch.no_grad():
+            self.qkv.bias[self.dim:2 * self.dim].zero_()
+
+    def forward(self, rows, Hf: int, Wf: int):
+        """rows [B Hf Wf, D] -> [B Hf Wf, D]"""
+        shift = 0 if min(Hf, Wf) <= self.window else self.shift  # one window: nothing to shift
+        qkv = Fn.linear_act(rows, self.qkv, dead_bias=(self.dim, 2 * self.dim))
+        if not qkv.is_contiguous():
+            qkv = qkv.contiguous()
+        mlp = self.cpb_mlp
+        bias = Fn.cpb_bias(mlp[0].weight, mlp[0].bias, mlp[2].weight, self.num_heads, self.window)
+        o = Fn.window_attention_cos(qkv, self.logit_scale, bias, self.num_heads, Hf, Wf, self.window, shift)
+        return Fn.linear_act(o, self.proj)
+
+    def extra_repr(self):
+        return "dim={}, window={}, shift={}, num_heads={}".format(self.dim, self.window, self.shift,
+                                                                  self.num_heads)
+
+
 class PatchEmbed(nn.Module):
     """ViT's patch embedding, a P x P / stride P conv, as patch rows times a [D, P P Cp] matrix
     (``Fn.patch_tokens``).  The state_dict holds torchvision's ``weight`` [D, C, P, P] and

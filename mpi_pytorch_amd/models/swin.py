@@ -16,6 +16,15 @@ where torchvision concatenates (0,0), (1,0), (0,1), (1,1): the ``norm`` vectors 
 
 Stochastic depth is not implemented: the model runs at rate 0 (torchvision's ``swin_t`` recipe
 uses 0.2), as ConvNeXt here does.  The model is built for maps the window divides.
+
+Swin-V2-T (torchvision ``swin_v2_t``, window 8 at 256 x 256) is the same network with three
+parts exchanged.  The attention is ``ShiftedWindowAttentionV2``: cosine scores times a clamped
+learned temperature, and a bias table that ``Fn.cpb_bias`` computes from a small MLP over
+log-spaced offsets (``Fn.window_attention_cos``, the cosine variant of the same kernels).  The
+block is residual-post-norm, ``x + norm1(attn(x))`` and ``x + norm2(mlp(x))``.  Patch merging
+normalises after the reduction: rows -> Linear(4 C, 2 C, bias=False) -> LayerNorm(2 C), with the
+same column permutation of ``reduction`` on import / export and a plain ``norm``.  Stochastic
+depth is not implemented here either (rate 0; torchvision's ``swin_v2_t`` recipe uses 0.2).
 """
 from __future__ import annotations
 
@@ -23,7 +32,8 @@ import torch
 import torch.nn as nn
 
 from ..ops import functional as Fn
-from .layers import GELU, LayerNorm, Linear, PatchEmbed, ShiftedWindowAttention
+from .layers import (GELU, LayerNorm, Linear, PatchEmbed, ShiftedWindowAttention,
+                     ShiftedWindowAttentionV2)
 
 
 def _cells(t):
@@ -80,10 +90,12 @@ class PatchMerging(nn.Module):
 
 
 class SwinBlock(nn.Module):
+    attention = ShiftedWindowAttention
+
     def __init__(self, dim: int, heads: int, window: int, shift: int, mlp_ratio: float = 4.0):
         super().__init__()
         self.norm1 = LayerNorm(dim, eps=1e-5)
-        self.attn = ShiftedWindowAttention(dim, window, shift, heads)
+        self.attn = self.attention(dim, window, shift, heads)
         self.norm2 = LayerNorm(dim, eps=1e-5)
         hidden = int(dim * mlp_ratio)
         # torchvision's MLP indices: 2 and 4 are its dropouts
@@ -98,19 +110,46 @@ class SwinBlock(nn.Module):
         return Fn.residual_add(Fn.linear_act(h, self.mlp[3]), x, join)
 
 
+class PatchMergingV2(nn.Module):
+    def __init__(self, dim: int):
+        super().__init__()
+        self.dim = dim
+        self.reduction = _MergeLinear(dim)
+        self.norm = LayerNorm(2 * dim, eps=1e-5)
+
+    def forward(self, rows, B: int, Hf: int, Wf: int):
+        """rows [B Hf Wf, C] -> [B Hf/2 Wf/2, 2 C]"""
+        x = Fn.patch_merge_rows(rows.reshape(B, Hf, Wf, self.dim))
+        return self.norm(Fn.linear_act(x, self.reduction))
+
+
+class SwinBlockV2(SwinBlock):
+    """Residual-post-norm: the LayerNorm follows the branch and its output is the residual
+    add's in-place operand (the LayerNorm's backward reads its input, not its output)."""
+
+    attention = ShiftedWindowAttentionV2
+
+    def forward(self, rows, Hf: int, Wf: int):
+        xb, join = Fn.residual_branch(rows)
+        x = Fn.residual_add(self.norm1(self.attn(xb, Hf, Wf)), rows, join)
+        xb, join = Fn.residual_branch(x)
+        h = Fn.linear_gelu(xb, self.mlp[0])
+        return Fn.residual_add(self.norm2(Fn.linear_act(h, self.mlp[3])), x, join)
+
+
 class SwinTransformer(nn.Module):
     def __init__(self, patch: int = 4, width: int = 96, depths=(2, 2, 6, 2), heads=(3, 6, 12, 24),
-                 window: int = 7, num_classes: int = 1000):
+                 window: int = 7, num_classes: int = 1000, block=SwinBlock, merge=PatchMerging):
         super().__init__()
         self.patch, self.width, self.window = patch, width, window
         # torchvision's indices: features.0 is (conv, permute, norm)
         layers = [nn.Sequential(PatchEmbed(3, width, patch), nn.Identity(), LayerNorm(width, eps=1e-5))]
         dim = width
         for s, (depth, nh) in enumerate(zip(depths, heads)):
-            layers.append(nn.Sequential(*[SwinBlock(dim, nh, window, 0 if i % 2 == 0 else window // 2)
+            layers.append(nn.Sequential(*[block(dim, nh, window, 0 if i % 2 == 0 else window // 2)
                                           for i in range(depth)]))
             if s + 1 < len(depths):
-                layers.append(PatchMerging(dim))
+                layers.append(merge(dim))
                 dim *= 2
         self.features = nn.Sequential(*layers)
         self.norm = LayerNorm(dim, eps=1e-5)
@@ -129,7 +168,7 @@ class SwinTransformer(nn.Module):
         stem = self.features[0]
         rows = stem[2](Fn.linear_act(Fn.K(x).patchify(stem[0].fit_input(x), P), stem[0]))
         for m in list(self.features)[1:]:
-            if isinstance(m, PatchMerging):
+            if isinstance(m, (PatchMerging, PatchMergingV2)):
                 rows = m(rows, B, Hf, Wf)
                 Hf, Wf = Hf // 2, Wf // 2
             else:
@@ -142,3 +181,9 @@ class SwinTransformer(nn.Module):
 
 def swin_t(num_classes: int = 1000) -> SwinTransformer:
     return SwinTransformer(num_classes=num_classes)
+
+
+def swin_v2_t(num_classes: int = 1000) -> SwinTransformer:
+    """torchvision's ``swin_v2_t``: patch 4, width 96, depths 2-2-6-2, heads 3-6-12-24, window 8
+    (256 x 256 images: maps 64, 32, 16, 8)."""
+    return SwinTransformer(window=8, num_classes=num_classes, block=SwinBlockV2, merge=PatchMergingV2)

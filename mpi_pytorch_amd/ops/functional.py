@@ -1221,6 +1221,74 @@ def window_attention(qkv, bias, heads: int, Hf: int, Wf: int, ws: int, shift: in
     return K(qkv).wattn_fwd(qkv, bias, heads, Hf, Wf, ws, shift)[0]
 
 
+class _WindowAttentionCos(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, qkv, bias, logit_scale, heads, Hf, Wf, ws, shift):
+        o, lse = K(qkv).wattn_cos_fwd(qkv, logit_scale, bias, heads, Hf, Wf, ws, shift)
+        ctx.logit_scale, ctx.geom = logit_scale, (heads, Hf, Wf, ws, shift)
+        ctx.save_for_backward(qkv, bias, lse)
+        return o
+
+    @staticmethod
+    def backward(ctx, do):
+        qkv, bias, lse = ctx.saved_tensors
+        ls, k = ctx.logit_scale, K(do)
+        do = do.contiguous()
+        # bias is an activation (cpb_bias's output): its gradient is returned, under the one
+        # overwrite flag it shares with the logit-scale gradient
+        if not ls.requires_grad:  # frozen: the logit-scale gradient into scratch
+            dls, fresh = torch.empty(ls.numel(), device=do.device, dtype=torch.float32), True
+        else:
+            dls, fresh = grad_sink(ls), _fresh(ls)
+        dbias = torch.empty_like(bias) if fresh else torch.zeros_like(bias)
+        dqkv = k.wattn_cos_bwd(do, qkv, lse, ls, bias, dbias, dls, *ctx.geom, fresh)
+        _done(ls)
+        return _grads(_WindowAttentionCos, dqkv, dbias)
+
+
+def window_attention_cos(qkv, logit_scale, bias, heads: int, Hf: int, Wf: int, ws: int, shift: int):
+    """Swin V2's attention over the rows ``qkv`` [B Hf Wf, 3 * heads * 32] in natural token order:
+    softmax(tau_h cos(q, k) + bias[h][rel] + shift mask) v inside every ws x ws window of the map
+    rolled by ``shift``, tau_h = exp(min(logit_scale[h], ln 100)).  ``logit_scale`` is a [heads] fp32
+    parameter, ``bias`` heads * (2 ws - 1)^2 fp32 (``cpb_bias``), differentiated through."""
+    if torch.is_grad_enabled() and (qkv.requires_grad or bias.requires_grad or logit_scale.requires_grad):
+        return _WindowAttentionCos.apply(qkv, bias, logit_scale, heads, Hf, Wf, ws, shift)
+    return K(qkv).wattn_cos_fwd(qkv, logit_scale, bias, heads, Hf, Wf, ws, shift)[0]
+
+
+class _CpbBias(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, w1, b1, w2, heads, ws):
+        bias = K(w1).cpb_fwd(w1, b1, w2, heads, ws)
+        ctx.params, ctx.geom = (w1, b1, w2), (heads, ws)
+        ctx.save_for_backward(bias)
+        return bias
+
+    @staticmethod
+    def backward(ctx, dbias):
+        (bias,) = ctx.saved_tensors
+        w1, b1, w2 = ctx.params
+        k = K(dbias)
+        dbias = dbias.contiguous()
+        if not (w1.requires_grad and b1.requires_grad and w2.requires_grad):  # frozen: into scratch
+            tmp = [torch.empty_like(p, dtype=torch.float32) for p in ctx.params]
+            k.cpb_bwd(dbias, bias, w1, b1, w2, *tmp, *ctx.geom, True)
+            return _grads(_CpbBias)
+        fresh = [_fresh(p) for p in ctx.params]
+        k.cpb_bwd(dbias, bias, w1, b1, w2, grad_sink(w1), grad_sink(b1), grad_sink(w2), *ctx.geom, all(fresh))
+        _done(w1, b1, w2)
+        return _grads(_CpbBias)
+
+
+def cpb_bias(w1, b1, w2, heads: int, ws: int):
+    """Swin V2's continuous position bias, [heads * (2 ws - 1)^2] fp32 head-major:
+    16 sigmoid(w2 relu(w1 coord + b1)) over the log-spaced relative coordinates of a ws x ws window
+    (``w1`` [512, 2], ``b1`` [512], ``w2`` [heads, 512], fp32 parameters)."""
+    if torch.is_grad_enabled() and (w1.requires_grad or b1.requires_grad or w2.requires_grad):
+        return _CpbBias.apply(w1, b1, w2, heads, ws)
+    return K(w1).cpb_fwd(w1, b1, w2, heads, ws)
+
+
 class _PatchMerge(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x):
@@ -1569,10 +1637,13 @@ def bn_relu_avgpool2(x, bn, stats: Optional[torch.Tensor] = None):
 # ================================================================================ linear
 class _LinearAct(torch.autograd.Function):
     """y = act(x W^T + b) over the layer's padded output width; returns the first
-    ``nout`` columns (a view) when the layer stores padded rows (layers.Linear)."""
+    ``nout`` columns (a view) when the layer stores padded rows (layers.Linear).  ``dead``: a
+    (begin, end) range of the bias that the model holds at zero (Swin V2's k bias): its
+    gradient is cleared before the bias is reported done."""
 
     @staticmethod
-    def forward(ctx, x, w, b, relu, nout):
+    def forward(ctx, x, w, b, relu, nout, dead=None):
+        ctx.dead = dead
         k = K(x)
         y = k.linear_fwd(x, weight_of(w), _or_empty(b, x), relu)
         ctx.relu = relu
@@ -1592,11 +1663,13 @@ class _LinearAct(torch.autograd.Function):
         # nothing waits for w.grad before its bucket closes
         dx = (k.linear_dgrad(g, weight_of(w), weight_t_of(w)) if ctx.needs_input_grad[0]
               else None)
+        if ctx.dead is not None and b is not None and b.requires_grad:
+            k.zero_f32(grad_sink(b)[ctx.dead[0]:ctx.dead[1]])
         _done(b)
         if w.requires_grad:
             k.linear_wgrad(g, x, w.grad, overwrite=_fresh(w))
             _done(w)
-        return dx, None, None, None, None
+        return dx, None, None, None, None, None
 
 
 def _padded_grad(dy, width: int):
@@ -1615,10 +1688,10 @@ def _padded_grad(dy, width: int):
     return torch.nn.functional.pad(dy, (0, width - dy.shape[1])).contiguous()
 
 
-def linear_act(x, lin, relu: bool = False):
+def linear_act(x, lin, relu: bool = False, dead_bias=None):
     nout = getattr(lin, "out_features", lin.weight.shape[0])
     if torch.is_grad_enabled() and (lin.weight.requires_grad or x.requires_grad):
-        return _LinearAct.apply(x, lin.weight, lin.bias, relu, nout)
+        return _LinearAct.apply(x, lin.weight, lin.bias, relu, nout, dead_bias)
     y = K(x).linear_fwd(x, weight_of(lin.weight), _or_empty(lin.bias, x), relu)
     return y if nout == y.shape[1] else y[:, :nout]
 

@@ -410,6 +410,95 @@ def wattn_bwd(do, qkv, lse, bias, dbias, heads, Hf, Wf, ws, shift, overwrite=Fal
     return window_reverse(w, Hf, Wf, ws, shift).contiguous().to(qkv.dtype)
 
 
+# ------------------------------------------- cosine window attention and position bias (Swin V2)
+WATTN_LOGIT_MAX = math.log(100.0)  # the clamp of logit_scale: a temperature of at most 100
+
+
+def _wattn_cos_operands(qkv, logit_scale, bias, heads, Hf, Wf, ws, shift):
+    """_wattn_operands, the inverse row norms rq, rk [B nW, H, ws^2, 1], the cosines c from the
+    raw product (the inverse norms multiply the fp32 accumulator) and the temperature [1, H, 1, 1]."""
+    if logit_scale.dtype != torch.float32 or logit_scale.numel() != heads:
+        raise ValueError("cosine window attention: logit_scale must be [H] float32")
+    q, k, v, add, mask, idx = _wattn_operands(qkv, bias, heads, Hf, Wf, ws, shift)
+    rq = 1.0 / q.norm(dim=-1, keepdim=True).clamp_min(1e-12)
+    rk = 1.0 / k.norm(dim=-1, keepdim=True).clamp_min(1e-12)
+    c = (q @ k.transpose(-1, -2)) * rq * rk.transpose(-1, -2)
+    tau = torch.clamp(logit_scale.reshape(1, heads, 1, 1), max=WATTN_LOGIT_MAX).exp()
+    return q, k, v, rq, rk, c, tau, add, mask, idx
+
+
+def wattn_cos_fwd(qkv, logit_scale, bias, heads, Hf, Wf, ws, shift):
+    """(o, lse) of softmax(tau_h cos(q_i, k_j) + bias + mask) v per window of the rolled map, tau_h
+    = exp(min(logit_scale[h], ln 100)), cos over rows divided by max(norm, 1e-12); layouts and
+    roundings as ``wattn_fwd``, the normalised rows are never rounded."""
+    q, k, v, _, _, c, tau, add, mask, _ = _wattn_cos_operands(qkv, logit_scale, bias, heads, Hf, Wf, ws, shift)
+    s = tau * c + add + mask
+    m = s.amax(-1, keepdim=True)
+    p = torch.exp(s - m)
+    l = p.sum(-1, keepdim=True)
+    o = ((_bfr(p) @ v) / l).permute(0, 2, 1, 3).reshape(-1, ws * ws, heads * 32)
+    return window_reverse(o, Hf, Wf, ws, shift).to(qkv.dtype), (m + torch.log(l)).squeeze(-1)
+
+
+def wattn_cos_bwd(do, qkv, lse, logit_scale, bias, dbias, dlogit, heads, Hf, Wf, ws, shift, overwrite=False):
+    """dqkv; dbias and dlogit (+)=.  With dS as in ``wattn_bwd``, t_i = sum_j dS c and u_j = sum_i
+    dS c: dQ_i = tau rq_i (sum_j dS rk_j k_j - t_i rq_i q_i) and the mirror image for dK, the
+    temperature and the other side's inverse norm folded into the bf16 operand; dlogit_h = tau_h
+    sum_i t_i below the clamp, 0 at it."""
+    q, k, v, rq, rk, c, tau, add, mask, idx = _wattn_cos_operands(qkv, logit_scale, bias, heads, Hf, Wf, ws, shift)
+    S2 = ws * ws
+    dof = window_partition(_f(do), Hf, Wf, ws, shift).reshape(-1, S2, heads, 32).permute(0, 2, 1, 3)
+    p = torch.exp(tau * c + add + mask - lse.unsqueeze(-1))
+    dp = dof @ v.transpose(-1, -2)
+    ds = p * (dp - (p * dp).sum(-1, keepdim=True))
+    t = (ds * c).sum(-1, keepdim=True)
+    u = (ds * c).sum(-2).unsqueeze(-1)
+    dv = _bfr(p).transpose(-1, -2) @ dof
+    dq = rq * (_bfr(ds * (tau * rk.transpose(-1, -2))) @ k - tau * t * rq * q)
+    dk = rk * (_bfr(ds * (tau * rq)).transpose(-1, -2) @ q - tau * u * rk * k)
+    db = torch.zeros(heads, (2 * ws - 1) ** 2, device=qkv.device)
+    db.index_add_(1, idx, ds.sum(0).reshape(heads, S2 * S2))
+    _acc(dbias.reshape(heads, -1), db, overwrite)
+    dl = t.sum((0, 2, 3)) * tau.reshape(-1)
+    _acc(dlogit.reshape(-1), torch.where(logit_scale.reshape(-1) < WATTN_LOGIT_MAX, dl, torch.zeros_like(dl)),
+         overwrite)
+    w = torch.stack([dq, dk, dv]).permute(1, 3, 0, 2, 4).reshape(-1, S2, 3 * heads * 32)
+    return window_reverse(w, Hf, Wf, ws, shift).contiguous().to(qkv.dtype)
+
+
+def _cpb_hidden(w1, b1, w2, heads, ws):
+    """coords [(2 ws - 1)^2, 2] in the closed form the kernel uses, and the pre-activation [T, 512]."""
+    if ws < 2 or ws * ws > 64 or heads < 1:
+        raise ValueError("position bias: heads > 0 and a window of 2 <= ws, ws^2 <= 64")
+    if tuple(w1.shape) != (512, 2) or b1.numel() != 512 or tuple(w2.shape) != (heads, 512):
+        raise ValueError("position bias: w1 [512, 2], b1 [512], w2 [H, 512]")
+    if any(t.dtype != torch.float32 for t in (w1, b1, w2)):
+        raise ValueError("position bias: w1, b1 and w2 must be float32")
+    t = torch.arange((2 * ws - 1) ** 2, device=w1.device)
+    d = torch.stack([t // (2 * ws - 1), t % (2 * ws - 1)], 1) - (ws - 1)
+    x = d.float() / (ws - 1) * 8
+    coords = torch.sign(x) * torch.log2(x.abs() + 1.0) / 3.0
+    return coords, coords @ w1.t() + b1.reshape(1, -1)
+
+
+def cpb_fwd(w1, b1, w2, heads, ws):
+    """[H (2 ws - 1)^2] fp32, head-major: 16 sigmoid(w2 relu(w1 coord + b1)) over torchvision's
+    log-spaced relative coordinates."""
+    _, pre = _cpb_hidden(w1, b1, w2, heads, ws)
+    return (16 * torch.sigmoid(torch.relu(pre) @ w2.t())).t().reshape(-1).contiguous()
+
+
+def cpb_bwd(dbias, bias, w1, b1, w2, dw1, db1, dw2, heads, ws, overwrite=False):
+    """dw1, db1, dw2 (+)= the MLP's gradients; the sigmoid's slope from the stored table."""
+    coords, pre = _cpb_hidden(w1, b1, w2, heads, ws)
+    b = bias.reshape(heads, -1)
+    dz = dbias.reshape(heads, -1) * b * (1 - b / 16)           # [H, T]
+    dh = (dz.t() @ w2) * (pre > 0)                             # [T, 512]
+    _acc(dw2, dz @ torch.relu(pre), overwrite)
+    _acc(dw1, dh.t() @ coords, overwrite)
+    _acc(db1.reshape(-1), dh.sum(0), overwrite)
+
+
 def tokens_fwd(patch, cls, pos):
     """[B, 1 + Np, D]: [cls | patch rows] + pos, fp32 add, one rounding."""
     D = patch.shape[1]
