@@ -639,23 +639,26 @@ Tensor ln_bwd(Tensor dy, Tensor x, Tensor pre_bias, Tensor gamma, Tensor stat, T
   return dx;
 }
 
-Tensor gelu_fwd(Tensor h) {
+// pre_bias (optional, [C] fp32): the bias of the op that produced h, added before the GELU
+Tensor gelu_fwd(Tensor h, c10::optional<Tensor> pre_bias) {
   const mpa::LnGeom g = ln_geom("gelu_fwd", h, false);
+  const float* pb = ln_vec("gelu_fwd", "pre_bias", pre_bias.value_or(Tensor()), g.C, true);
   const c10::OptionalDeviceGuard guard(device_of(h));
   Tensor a = torch::empty_like(h);
-  mpa::gelu_fwd(bp(h), g, bpm(a), cur_stream());
+  mpa::gelu_fwd(bp(h), g, bpm(a), cur_stream(), pb);
   return a;
 }
 
-Tensor gelu_bwd(Tensor da, Tensor h, Tensor dbias) {
+Tensor gelu_bwd(Tensor da, Tensor h, Tensor dbias, c10::optional<Tensor> pre_bias) {
   const mpa::LnGeom g = ln_geom("gelu_bwd", h, false);
   ln_same("gelu_bwd", "da", da, h);
   float* db = ln_vec("gelu_bwd", "dbias", dbias, g.C, true);
+  const float* pb = ln_vec("gelu_bwd", "pre_bias", pre_bias.value_or(Tensor()), g.C, true);
   const c10::OptionalDeviceGuard guard(device_of(h));
   Tensor dh = torch::empty_like(h);
   Tensor ws;
   float* wsp = db ? alloc_ws(ws, h, mpa::ln_col_ws_floats(g)) : nullptr;
-  mpa::gelu_bwd(bp(da), bp(h), g, bpm(dh), db, wsp, cur_stream());
+  mpa::gelu_bwd(bp(da), bp(h), g, bpm(dh), db, wsp, cur_stream(), pb);
   return dh;
 }
 
@@ -764,6 +767,64 @@ Tensor unpatchify(Tensor rows, int64_t Hi, int64_t Wi, int64_t P) {
   Tensor x = empty_like_shape(rows, {g.B, g.Hi, g.Wi, g.Cp}, torch::kBFloat16);
   mpa::unpatchify(bp(rows), g, bpm(x), cur_stream());
   return x;
+}
+
+// ------------------------------------------------- short-key cross-attention (xattn.hip)
+// q [B, Sq, H 64] and kv [B, Sk, 2 H 64] bf16 contiguous, Sk <= 64.  Anything the kernels do not
+// serve is refused here, before an output exists.
+static mpa::XattnGeom xattn_geom(const char* op, const Tensor& q, const Tensor& kv, int64_t heads) {
+  CHECK_ACT(q);
+  CHECK_ACT(kv);
+  TORCH_CHECK(q.dim() == 3 && kv.dim() == 3 && heads > 0 && heads < 65536, op,
+              ": q must be [B, Sq, heads * 64] and kv [B, Sk, 2 * heads * 64]");
+  TORCH_CHECK(q.size(2) == heads * mpa::AT_D && kv.size(2) == 2 * heads * mpa::AT_D, op,
+              ": last dimensions must be heads * 64 and 2 * heads * 64 (head dim 64), got ", q.size(2),
+              " and ", kv.size(2));
+  TORCH_CHECK(q.size(0) == kv.size(0), op, ": q and kv differ in batch");
+  TORCH_CHECK(q.size(0) < ((int64_t)1 << 31) && q.size(1) < ((int64_t)1 << 31) &&
+                  kv.size(1) < ((int64_t)1 << 31), op, ": tensor too large");
+  const mpa::XattnGeom g{(int)q.size(0), (int)q.size(1), (int)kv.size(1), (int)heads};
+  const char* err = mpa::xattn_geom_error(g);
+  TORCH_CHECK(!err, op, ": ", err);
+  TORCH_CHECK(aligned16(q) && aligned16(kv), op, ": q and kv must be 16-byte aligned");
+  return g;
+}
+
+std::vector<Tensor> xattn_fwd(Tensor q, Tensor kv, int64_t heads) {
+  const mpa::XattnGeom g = xattn_geom("xattn_fwd", q, kv, heads);
+  const c10::OptionalDeviceGuard guard(device_of(q));
+  Tensor o = torch::empty_like(q);
+  Tensor lse = empty_like_shape(q, {g.B, g.H, g.Sq}, torch::kFloat32);
+  mpa::xattn_fwd(bp(q), bp(kv), g, bpm(o), lse.data_ptr<float>(), cur_stream());
+  return {o, lse};
+}
+
+std::vector<Tensor> xattn_bwd(Tensor d_o, Tensor q, Tensor kv, Tensor o, Tensor lse, int64_t heads) {
+  const mpa::XattnGeom g = xattn_geom("xattn_bwd", q, kv, heads);
+  CHECK_ACT(d_o);
+  CHECK_ACT(o);
+  TORCH_CHECK(d_o.numel() == q.numel() && o.numel() == q.numel() && aligned16(d_o) && aligned16(o),
+              "xattn_bwd: do and o must be [B, Sq, H 64]");
+  TORCH_CHECK(has(lse) && lse.numel() == (int64_t)g.B * g.H * g.Sq, "xattn_bwd: lse must be [B, H, Sq]");
+  const float* lp = fopt(lse);
+  const c10::OptionalDeviceGuard guard(device_of(q));
+  Tensor dq = torch::empty_like(q);
+  Tensor dkv = torch::empty_like(kv);
+  Tensor ws;
+  float* wsp = alloc_ws(ws, q, mpa::xattn_ws_floats(g));
+  mpa::xattn_bwd(bp(d_o), bp(q), bp(kv), bp(o), lp, g, bpm(dq), bpm(dkv), wsp, cur_stream());
+  return {dq, dkv};
+}
+
+// (tiles per walk, walks = dK / dV slab rows per (batch, head), workspace floats) of a geometry
+std::vector<int64_t> xattn_plan(int64_t B, int64_t H, int64_t Sq, int64_t Sk) {
+  TORCH_CHECK(B > 0 && H > 0 && Sq > 0 && Sk > 0 && B < 65536 && H < 65536 && Sq < ((int64_t)1 << 31) &&
+                  Sk < ((int64_t)1 << 31), "xattn_plan: geometry out of range");
+  const mpa::XattnGeom g{(int)B, (int)Sq, (int)Sk, (int)H};
+  const char* err = mpa::xattn_geom_error(g);
+  TORCH_CHECK(!err, "xattn_plan: ", err);
+  const mpa::XattnPlan p = mpa::xattn_plan(g);
+  return {p.tpw, p.walks, p.ws_floats};
 }
 
 // ------------------------------------------------------ shifted-window attention (wattn.hip)
@@ -2708,9 +2769,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("ln_bwd", &ln_bwd, py::arg("dy"), py::arg("x"), py::arg("pre_bias"), py::arg("gamma"),
         py::arg("stat"), py::arg("dgamma"), py::arg("dbeta"), py::arg("dpre_bias"),
         py::arg("overwrite") = false);
-  m.def("gelu_fwd", &gelu_fwd, py::arg("h"), "exact (erf) GELU");
+  m.def("gelu_fwd", &gelu_fwd, py::arg("h"), py::arg("pre_bias") = py::none(),
+        "exact (erf) GELU of h (+ pre_bias[c])");
   m.def("gelu_bwd", &gelu_bwd, py::arg("da"), py::arg("h"), py::arg("dbias"),
-        "dh = da gelu'(h); dbias += column sums of dh");
+        py::arg("pre_bias") = py::none(), "dh = da gelu'(h (+ pre_bias[c])); dbias += column sums of dh");
   m.def("scale_add_fwd", &scale_add_fwd, py::arg("y"), py::arg("gamma"), py::arg("res"),
         "res + gamma[c] y");
   m.def("scale_add_bwd", &scale_add_bwd, py::arg("dout"), py::arg("y"), py::arg("gamma"),
@@ -2727,6 +2789,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("overwrite") = false, "dpatch = dx[:, 1:]; dcls, dpos (+)= sums over the batch");
   m.def("unpatchify", &unpatchify, py::arg("rows"), py::arg("Hi"), py::arg("Wi"), py::arg("P"),
         "the NHWC image [B, Hi, Wi, C] of patch rows: patchify's inverse");
+  m.def("xattn_fwd", &xattn_fwd, py::arg("q"), py::arg("kv"), py::arg("heads"),
+        "(o, lse): attention of q [B, Sq, H 64] over the keys and values kv [B, Sk <= 64, 2 H 64]");
+  m.def("xattn_bwd", &xattn_bwd, py::arg("do"), py::arg("q"), py::arg("kv"), py::arg("o"),
+        py::arg("lse"), py::arg("heads"), "(dq, dkv) in q's and kv's layouts");
+  m.def("xattn_plan", &xattn_plan, py::arg("B"), py::arg("H"), py::arg("Sq"), py::arg("Sk"),
+        "(tiles per walk, walks, workspace floats) of xattn_fwd / xattn_bwd");
   m.def("wattn_fwd", &wattn_fwd, py::arg("qkv"), py::arg("bias"), py::arg("heads"), py::arg("Hf"),
         py::arg("Wf"), py::arg("ws"), py::arg("shift"),
         "(o, lse): shifted-window attention over the rows qkv [B Hf Wf, 3 H 32] in token order");

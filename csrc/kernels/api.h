@@ -14,6 +14,7 @@
 #include "ln_plan.h"
 #include "attn_plan.h"
 #include "wattn_plan.h"
+#include "xattn_plan.h"
 
 namespace mpa {
 
@@ -140,9 +141,12 @@ void ln_bwd(const bf16_raw* dy, const bf16_raw* x, const float* pre_bias, const 
             float* dpre_bias, bool overwrite, float* ws, hipStream_t s);
 // a = h Phi(h) (erf form); dh = da (Phi(h) + h phi(h)), dbias [C] (optional) += column sums of
 // the stored dh; ws holds ln_col_ws_floats(g) floats when dbias is set (ln_col_error(g) == nullptr)
-void gelu_fwd(const bf16_raw* h, const LnGeom& g, bf16_raw* a, hipStream_t s);
+// pre_bias [C] (optional): both act on h + pre_bias[c] (fp32 sum, no rounding of its own), and
+// dbias is then that bias's gradient
+void gelu_fwd(const bf16_raw* h, const LnGeom& g, bf16_raw* a, hipStream_t s,
+              const float* pre_bias = nullptr);
 void gelu_bwd(const bf16_raw* da, const bf16_raw* h, const LnGeom& g, bf16_raw* dh, float* dbias,
-              float* ws, hipStream_t s);
+              float* ws, hipStream_t s, const float* pre_bias = nullptr);
 // out = res + gamma[c] y; dy = gamma[c] dout, dgamma [C] (+)= column sums of dout y
 void scale_add_fwd(const bf16_raw* y, const float* gamma, const bf16_raw* res, const LnGeom& g,
                    bf16_raw* out, hipStream_t s);
@@ -167,6 +171,18 @@ void tokens_bwd(const bf16_raw* dx, const TokGeom& g, bf16_raw* dpatch, float* d
                 bool overwrite, hipStream_t s);
 // patchify's inverse permutation: x [B][Hi][Wi][Cp] from rows (patchify's backward)
 void unpatchify(const bf16_raw* rows, const PatchGeom& g, bf16_raw* x, hipStream_t s);
+
+// xattn.hip: cross-attention with a short key set (xattn_geom_error(g) == nullptr), planned by
+// xattn_plan.h.  q [B][Sq][H][64], kv [B][Sk][2][H][64] (k rows, then v rows, heads of 64 inside
+// each), 1 <= Sk <= 64, scale 1/8, no mask, no dropout.  o [B][Sq][H 64] bf16, lse [B][H][Sq] fp32.
+void xattn_fwd(const bf16_raw* q, const bf16_raw* kv, const XattnGeom& g, bf16_raw* o, float* lse,
+               hipStream_t s);
+// dq has q's layout, dkv has kv's; both written whole.  ws holds xattn_ws_floats(g) floats.
+// No float atomics: one attention pass, then a fixed-order sum of its dK / dV slab rows.
+int64_t xattn_ws_floats(const XattnGeom& g);
+void xattn_bwd(const bf16_raw* d_o, const bf16_raw* q, const bf16_raw* kv, const bf16_raw* o,
+               const float* lse, const XattnGeom& g, bf16_raw* dq, bf16_raw* dkv, float* ws,
+               hipStream_t s);
 
 // wattn.hip: shifted-window attention over the in-projection's rows qkv [B Hf Wf][3][H][32] bf16
 // in natural token order (wattn_geom_error(g) == nullptr), planned by wattn_plan.h:

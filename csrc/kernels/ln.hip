@@ -246,12 +246,21 @@ __device__ __forceinline__ float gelu_der(float h) {
   return fmaf(h, pdf, cdf);
 }
 
+// PRE: a = gelu(h + pre_bias[c]), the sum in fp32 (no rounding between it and the GELU)
+template <bool PRE>
 __global__ __launch_bounds__(256) void gelu_fwd_kernel(const bf16_t* __restrict__ h,
-                                                       bf16_t* __restrict__ out, int64_t nvec) {
+                                                       const float* __restrict__ pre_bias,
+                                                       bf16_t* __restrict__ out, int64_t nvec,
+                                                       int CV) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= nvec) return;
   float f[8];
   unpack8(ld_stream(h + i * 8), f);
+  if (PRE) {
+    const int cv = (int)(i % CV);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) f[j] += pre_bias[cv * 8 + j];
+  }
 #pragma unroll
   for (int j = 0; j < 8; ++j) f[j] = gelu_f(f[j]);
   st_stream(out + i * 8, pack8(f));
@@ -278,25 +287,27 @@ struct ColArgs {
   const bf16_t* g;      // da / dout
   const bf16_t* src;    // h / y
   const float* gamma;   // scale_add
+  const float* pre;     // gelu: pre_bias (PRE)
   bf16_t* out;          // dh / dy
   float* slab;          // [rows][C] or null (no column sums wanted)
   int M, C, CV, cvb, chunks, nslots, slab_rows;
 };
 
-// SCALE false: dh = da gelu'(h), column sums of the stored dh.
+// SCALE false: dh = da gelu'(h), column sums of the stored dh; PRE: gelu'(h + pre[c]).
 // SCALE true:  dy = gamma dout, column sums of dout y.
-template <bool SCALE>
+template <bool SCALE, bool PRE>
 __global__ __launch_bounds__(LN_THREADS) void col_bwd_kernel(ColArgs a) {
   __shared__ float red[8 * LN_THREADS];
   const int tid = threadIdx.x;
   const int chunk = blockIdx.x % a.chunks, sr = blockIdx.x / a.chunks;
   const int cv = tid % a.cvb, slot = tid / a.cvb, c0v = chunk * a.cvb;
   const bool on = slot < a.nslots && c0v + cv < a.CV;
-  float acc[8], gm[8];
+  float acc[8], gm[8], pb[8];
 #pragma unroll
   for (int j = 0; j < 8; ++j) {
     acc[j] = 0.f;
     gm[j] = (SCALE && on) ? a.gamma[(c0v + cv) * 8 + j] : 0.f;
+    pb[j] = (PRE && on) ? a.pre[(c0v + cv) * 8 + j] : 0.f;
   }
   if (on) {
     const int r1 = min(a.M, (sr + 1) * a.slab_rows);
@@ -305,6 +316,10 @@ __global__ __launch_bounds__(LN_THREADS) void col_bwd_kernel(ColArgs a) {
       float gf[8], sf[8], o[8];
       unpack8(ld_stream(a.g + ofs), gf);
       unpack8(ld_stream(a.src + ofs), sf);
+      if (PRE) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) sf[j] += pb[j];
+      }
 #pragma unroll
       for (int j = 0; j < 8; ++j) o[j] = SCALE ? gm[j] * gf[j] : gf[j] * gelu_der(sf[j]);
       const uint4 w = pack8(o);
@@ -331,16 +346,17 @@ __global__ __launch_bounds__(LN_THREADS) void col_bwd_kernel(ColArgs a) {
   }
 }
 
-template <bool SCALE>
+template <bool SCALE, bool PRE = false>
 void col_bwd(const bf16_raw* g, const bf16_raw* src, const float* gamma, const LnGeom& geom,
-             bf16_raw* out, float* sums, bool overwrite, float* ws, hipStream_t s) {
+             bf16_raw* out, float* sums, bool overwrite, float* ws, hipStream_t s,
+             const float* pre = nullptr) {
   const ColPlan p = ln_col_plan(geom);
   ColArgs a{};
-  a.g = g; a.src = src; a.gamma = gamma; a.out = out;
+  a.g = g; a.src = src; a.gamma = gamma; a.pre = pre; a.out = out;
   a.slab = sums ? ws : nullptr;
   a.M = geom.M; a.C = geom.C; a.CV = geom.C / 8;
   a.cvb = p.cvb; a.chunks = p.chunks; a.nslots = p.nslots; a.slab_rows = p.slab;
-  hipLaunchKernelGGL(col_bwd_kernel<SCALE>, dim3((unsigned)p.grid), dim3(LN_THREADS), 0, s, a);
+  hipLaunchKernelGGL((col_bwd_kernel<SCALE, PRE>), dim3((unsigned)p.grid), dim3(LN_THREADS), 0, s, a);
   MPA_CHECK_LAUNCH();
   if (sums) reduce_slab(ws, p.rows, geom.C, geom.C, LnOuts{{sums, nullptr, nullptr}}, overwrite, s);
 }
@@ -391,16 +407,19 @@ void ln_bwd(const bf16_raw* dy, const bf16_raw* x, const float* pre_bias, const 
   reduce_slab(ws, p.rows, a.width, g.C, LnOuts{{dgamma, dbeta, dpre_bias}}, overwrite, s);
 }
 
-void gelu_fwd(const bf16_raw* h, const LnGeom& g, bf16_raw* out, hipStream_t s) {
+void gelu_fwd(const bf16_raw* h, const LnGeom& g, bf16_raw* out, hipStream_t s,
+              const float* pre_bias) {
   const int64_t nvec = (int64_t)g.M * (g.C / 8);
-  hipLaunchKernelGGL(gelu_fwd_kernel, dim3((unsigned)((nvec + 255) / 256)), dim3(256), 0, s, h, out,
-                     nvec);
+  const dim3 grid((unsigned)((nvec + 255) / 256)), block(256);
+  if (pre_bias) hipLaunchKernelGGL(gelu_fwd_kernel<true>, grid, block, 0, s, h, pre_bias, out, nvec, g.C / 8);
+  else hipLaunchKernelGGL(gelu_fwd_kernel<false>, grid, block, 0, s, h, pre_bias, out, nvec, g.C / 8);
   MPA_CHECK_LAUNCH();
 }
 
 void gelu_bwd(const bf16_raw* da, const bf16_raw* h, const LnGeom& g, bf16_raw* dh, float* dbias,
-              float* ws, hipStream_t s) {
-  col_bwd<false>(da, h, nullptr, g, dh, dbias, false, ws, s);
+              float* ws, hipStream_t s, const float* pre_bias) {
+  if (pre_bias) col_bwd<false, true>(da, h, nullptr, g, dh, dbias, false, ws, s, pre_bias);
+  else col_bwd<false>(da, h, nullptr, g, dh, dbias, false, ws, s);
 }
 
 void scale_add_fwd(const bf16_raw* y, const float* gamma, const bf16_raw* res, const LnGeom& g,

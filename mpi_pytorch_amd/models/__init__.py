@@ -33,6 +33,7 @@ from .mobilenetv3 import mobilenet_v3_large, MobileNetV3
 from .convnext import convnext_tiny, ConvNeXt
 from .vit import vit_b_16, VisionTransformer
 from .swin import swin_t, swin_v2_t, SwinTransformer
+from .pvt import pvt_v2_b2, PyramidVisionTransformerV2
 
 ARCH = {
     "resnet18": ("resnet18", resnet18, 224),
@@ -83,6 +84,12 @@ WINDOW_V2_ARCH = {
     "swin_v2": ("swin_v2_t", swin_v2_t, 256),
 }
 
+# Architectures on the short-key cross-attention kernels (xattn.hip), looked up after
+# WINDOW_V2_ARCH.
+PYRAMID_ARCH = {
+    "pvt_v2": ("pvt_v2_b2", pvt_v2_b2, 224),
+}
+
 
 def set_parameter_requires_grad(model: nn.Module, feature_extracting: bool) -> None:
     if feature_extracting:
@@ -106,7 +113,7 @@ def initialize_model(model_name: str, num_classes: int, feature_extract: bool,
     entry = (ARCH.get(model_name) or EXTRA_ARCH.get(model_name) or SE_ARCH.get(model_name)
              or GROUPED_ARCH.get(model_name) or LN_ARCH.get(model_name)
              or ATTN_ARCH.get(model_name) or WINDOW_ARCH.get(model_name)
-             or WINDOW_V2_ARCH.get(model_name))
+             or WINDOW_V2_ARCH.get(model_name) or PYRAMID_ARCH.get(model_name))
     if entry is None:
         raise ValueError("Invalid model name {!r}".format(model_name))
     arch, ctor, input_size = entry
@@ -133,7 +140,7 @@ def initialize_model(model_name: str, num_classes: int, feature_extract: bool,
         model.classifier[2] = Linear(model.classifier[2].in_features, num_classes)
     elif model_name == "vit":
         model.heads.head = Linear(model.heads.head.in_features, num_classes)
-    elif model_name in ("swin", "swin_v2"):
+    elif model_name in ("swin", "swin_v2", "pvt_v2"):
         model.head = Linear(model.head.in_features, num_classes)
     return model, input_size
 
@@ -158,7 +165,7 @@ def head_parameters(model: nn.Module):
 
 
 __all__ = ["initialize_model", "set_parameter_requires_grad", "ARCH", "EXTRA_ARCH", "SE_ARCH",
-           "GROUPED_ARCH", "LN_ARCH", "ATTN_ARCH", "WINDOW_ARCH", "WINDOW_V2_ARCH", "convnext_tiny", "vit_b_16", "swin_t", "swin_v2_t", "InceptionOutputs", "mnasnet1_0", "mobilenet_v3_large",
+           "GROUPED_ARCH", "LN_ARCH", "ATTN_ARCH", "WINDOW_ARCH", "WINDOW_V2_ARCH", "PYRAMID_ARCH", "convnext_tiny", "vit_b_16", "swin_t", "swin_v2_t", "pvt_v2_b2", "InceptionOutputs", "mnasnet1_0", "mobilenet_v3_large",
            "resnext50_32x4d",
            "input_spec",
            "resnet18", "resnet34", "vgg11_bn", "vgg16", "alexnet", "squeezenet1_0",

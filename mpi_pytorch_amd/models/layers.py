@@ -555,6 +555,52 @@ class ShiftedWindowAttention(nn.Module):
                                                                   self.num_heads)
 
 
+class SpatialReductionAttention(nn.Module):
+    """PVT v2's attention with the official names: ``q``, ``kv``, ``proj`` and, where ``sr_ratio``
+    > 1, the reduction ``sr`` (a conv with kernel = stride = sr_ratio, run as ``Fn.patch_rows`` and
+    the rows GEMM: the strided-conv dgrad serves at most 16 stride phases, stride 8 has 64) and its
+    LayerNorm ``norm``.  The map must be a multiple of sr_ratio (the official conv drops the rest).
+    Head dim 64.  Every token of the map is a query; keys and values come from the reduced map,
+    at most 64 tokens (``Fn.cross_attention``).  The q rows [B Hf Wf, D] and the kv rows [B Sk,
+    2 D] are the kernel's inputs as they are, and its output the out-projection's rows."""
+
+    MAX_KEYS = 64
+
+    def __init__(self, dim: int, num_heads: int, sr_ratio: int = 1):
+        super().__init__()
+        if dim != 64 * num_heads:
+            raise ValueError("SpatialReductionAttention: head dim must be 64 (dim = 64 * num_heads)")
+        self.dim, self.num_heads, self.sr_ratio = dim, num_heads, sr_ratio
+        self.q = Linear(dim, dim)
+        self.kv = Linear(dim, 2 * dim)
+        self.proj = Linear(dim, dim)
+        if sr_ratio > 1:
+            # kernel = stride: ``patchify`` and the rows GEMM, weight OIHW in the state_dict
+            self.sr = PatchEmbed(dim, dim, sr_ratio, cin_store=dim)
+            self.norm = LayerNorm(dim, eps=1e-5)
+
+    def forward(self, x):
+        """x [B, Hf, Wf, D] -> [B, Hf, Wf, D]"""
+        B, Hf, Wf, D = x.shape
+        r = self.sr_ratio
+        if Hf % r or Wf % r:
+            raise ValueError("SpatialReductionAttention: the map must be a multiple of sr_ratio")
+        Sk = (Hf // r) * (Wf // r)
+        if not 1 <= Sk <= self.MAX_KEYS:
+            raise ValueError("SpatialReductionAttention: the reduced map holds {} tokens; the "
+                             "attention kernel serves 1 to {} keys".format(Sk, self.MAX_KEYS))
+        xq, xk = Fn.fan_out(x, 2)
+        q = Fn.linear_act(xq.reshape(B * Hf * Wf, D), self.q)
+        if r > 1:
+            xk = self.norm(Fn.linear_act(Fn.patch_rows(xk, r), self.sr))
+        kv = Fn.linear_act(xk.reshape(B * Sk, D), self.kv)
+        o = Fn.cross_attention(q.reshape(B, Hf * Wf, D), kv.reshape(B, Sk, 2 * D), self.num_heads)
+        return Fn.linear_act(o.reshape(B * Hf * Wf, D), self.proj).reshape(B, Hf, Wf, D)
+
+    def extra_repr(self):
+        return "dim={}, num_heads={}, sr_ratio={}".format(self.dim, self.num_heads, self.sr_ratio)
+
+
 class _MlpLayer(nn.Module):
     """``weight`` [out, in] and ``bias`` of one layer of the position-bias MLP, stored as they
     are (fp32, no pad rows): ``Fn.cpb_bias`` reads both layers in one kernel."""

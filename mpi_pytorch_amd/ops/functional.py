@@ -1157,6 +1157,61 @@ def attention(qkv, heads: int):
     return K(qkv).attn_fwd(qkv, heads)[0]
 
 
+class _CrossAttention(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, q, kv, heads):
+        o, lse = K(q).xattn_fwd(q, kv, heads)
+        ctx.heads = heads
+        ctx.save_for_backward(q, kv, o, lse)
+        return o
+
+    @staticmethod
+    def backward(ctx, do):
+        q, kv, o, lse = ctx.saved_tensors
+        dq, dkv = K(do).xattn_bwd(do.contiguous(), q, kv, o, lse, ctx.heads)
+        return dq, dkv, None
+
+
+def cross_attention(q, kv, heads: int):
+    """Attention of the queries ``q`` [B, Sq, heads * 64] over a short key set ``kv`` [B, Sk, 2 *
+    heads * 64] (k, then v row blocks, heads of 64 inside each), Sk <= 64: [B, Sq, heads * 64],
+    scale 1/8, no mask, no dropout (PVT v2's spatial-reduction attention)."""
+    if torch.is_grad_enabled() and (q.requires_grad or kv.requires_grad):
+        return _CrossAttention.apply(q, kv, heads)
+    return K(q).xattn_fwd(q, kv, heads)[0]
+
+
+class _BiasGelu(torch.autograd.Function):
+    """gelu(h + b): h is kept, and the GELU backward reduces b's gradient from the dh it stores."""
+
+    @staticmethod
+    def forward(ctx, h, b):
+        ctx.b = b
+        ctx.save_for_backward(h)
+        return K(h).gelu_fwd(h, b)
+
+    @staticmethod
+    def backward(ctx, da):
+        (h,) = ctx.saved_tensors
+        b = ctx.b
+        dh = K(da).gelu_bwd(da.contiguous(), h, _sink(b, da), b)
+        _done(b)
+        return dh, None
+
+
+def dwconv_gelu(x, conv):
+    """gelu(dwconv(x) + conv.bias): the conv runs bias-free and the GELU kernel adds the bias in
+    fp32 (PVT v2's MLP)."""
+    if not conv.depthwise or conv.bias is None:
+        raise ValueError("dwconv_gelu: a depthwise Conv2d (groups == channels) with a bias expected")
+    if torch.is_grad_enabled() and (conv.weight.requires_grad or x.requires_grad):
+        return _BiasGelu.apply(_DwConv.apply(x, conv.weight, conv, None, None, None), conv.bias)
+    sh, sw, ph, pw = conv.kgeom
+    k = K(x)
+    return k.gelu_fwd(k.dwconv_fwd(x, weight_of(conv.weight), sh, sw, ph, pw, _empty(x), _empty(x)),
+                      conv.bias)
+
+
 class _Tokens(torch.autograd.Function):
     @staticmethod
     def forward(ctx, patch, cls, pos):
@@ -1291,13 +1346,21 @@ def cpb_bias(w1, b1, w2, heads: int, ws: int):
 
 class _PatchMerge(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x):
-        ctx.hw = (x.shape[1], x.shape[2])
-        return K(x).patchify(x, 2)
+    def forward(ctx, x, P=2):
+        ctx.hw, ctx.P = (x.shape[1], x.shape[2]), P
+        return K(x).patchify(x, P)
 
     @staticmethod
     def backward(ctx, drows):
-        return K(drows).unpatchify(drows.contiguous(), ctx.hw[0], ctx.hw[1], 2)
+        return K(drows).unpatchify(drows.contiguous(), ctx.hw[0], ctx.hw[1], ctx.P), None
+
+
+def patch_rows(x, P: int):
+    """NHWC [B, Hf, Wf, C] -> rows [B Hf/P Wf/P, P P C], each P x P cell in (ky, kx, c) order: the
+    rows GEMM over them is the conv with kernel = stride = P (PVT's spatial reduction)."""
+    if torch.is_grad_enabled() and x.requires_grad:
+        return _PatchMerge.apply(x, P)
+    return K(x).patchify(x, P)
 
 
 def patch_merge_rows(x):
@@ -1349,6 +1412,15 @@ def residual_branch(x):
         join = GradJoin(2)
         return _JoinInput.apply(x, join), join
     return x, None
+
+
+def fan_out(x, n: int = 2):
+    """``n`` views of an activation that feeds ``n`` ops (PVT's normalised tokens: the query
+    projection and the key / value path): their input gradients meet in one join."""
+    if torch.is_grad_enabled() and x.requires_grad:
+        join = GradJoin(n)
+        return tuple(_JoinInput.apply(x, join) for _ in range(n))
+    return (x,) * n
 
 
 def residual_add(y, x, join: Optional[GradJoin] = None):

@@ -210,13 +210,15 @@ def ln_bwd(dy, x, pre_bias, gamma, stat, dgamma, dbeta, dpre_bias, overwrite=Fal
     return dx
 
 
-def gelu_fwd(h):
-    return F.gelu(_f(h)).to(h.dtype)
+def gelu_fwd(h, pre_bias=None):
+    """gelu(h + pre_bias[c]); the sum is not rounded."""
+    return F.gelu(_ln_t(h, pre_bias)).to(h.dtype)
 
 
-def gelu_bwd(da, h, dbias):
-    """dh = da (Phi(h) + h phi(h)); dbias (optional) += column sums of the stored dh."""
-    hf = _f(h)
+def gelu_bwd(da, h, dbias, pre_bias=None):
+    """dh = da (Phi(t) + t phi(t)), t = h + pre_bias[c]; dbias (optional) += column sums of the
+    stored dh."""
+    hf = _ln_t(h, pre_bias)
     cdf = 0.5 * (1.0 + torch.erf(hf * 0.7071067811865476))
     pdf = torch.exp(-0.5 * hf * hf) * 0.3989422804014327
     dh = (_f(da) * (cdf + hf * pdf)).to(da.dtype)
@@ -283,6 +285,54 @@ def attn_bwd(do, qkv, o, lse, heads=0):
     dq = (ds @ k) * 0.125
     dk = (ds.transpose(-1, -2) @ q) * 0.125
     return torch.stack([dq, dk, dv]).permute(1, 3, 0, 2, 4).reshape(qkv.shape).contiguous().to(qkv.dtype)
+
+
+def _xattn_qkv(q, kv, heads):
+    """q [B, H, Sq, 64] and k, v [B, H, Sk, 64] fp32 views of q [B, Sq, H 64], kv [B, Sk, 2 H 64]."""
+    if (q.dim() != 3 or kv.dim() != 3 or heads < 1 or q.shape[2] != heads * 64
+            or kv.shape[2] != 2 * heads * 64 or q.shape[0] != kv.shape[0]):
+        raise ValueError("cross attention: q [B, Sq, heads * 64] and kv [B, Sk, 2 * heads * 64] (head dim 64)")
+    if not (q.is_contiguous() and kv.is_contiguous()):
+        raise ValueError("cross attention: q and kv must be contiguous")
+    if q.numel() == 0 or kv.numel() == 0:
+        raise ValueError("cross attention: empty batch, sequence or no heads")
+    if kv.shape[1] > 64:
+        raise ValueError("cross attention: at most 64 keys (Sk <= 64)")
+    if not q.is_floating_point() or q.dtype == torch.float64 or kv.dtype != q.dtype:
+        raise ValueError("cross attention: q and kv must be bf16 (fp32 on the CPU path)")
+    B, Sq, Sk = q.shape[0], q.shape[1], kv.shape[1]
+    qh = _f(q).reshape(B, Sq, heads, 64).permute(0, 2, 1, 3)
+    k, v = _f(kv).reshape(B, Sk, 2, heads, 64).permute(2, 0, 3, 1, 4)
+    return qh, k, v
+
+
+def xattn_fwd(q, kv, heads):
+    """(o [B, Sq, H 64], lse [B, H, Sq]): softmax(q k^T / 8) v per head over kv's Sk <= 64 keys.
+    Scores, maximum, sum and lse in fp32; P is rounded to bf16 as the P V operand, the row sum
+    uses the unrounded P."""
+    qh, k, v = _xattn_qkv(q, kv, heads)
+    s = (qh @ k.transpose(-1, -2)) * 0.125
+    m = s.amax(-1, keepdim=True)
+    p = torch.exp(s - m)
+    l = p.sum(-1, keepdim=True)
+    o = (_bfr(p) @ v) / l
+    return o.permute(0, 2, 1, 3).reshape(q.shape).to(q.dtype), (m + torch.log(l)).squeeze(-1)
+
+
+def xattn_bwd(do, q, kv, o, lse, heads):
+    """(dq, dkv) in q's and kv's layouts: P = exp(s - lse) recomputed, delta = sum_d dO O in fp32,
+    dV = bf16(P)^T dO, dS = P (dO V^T - delta), dQ = bf16(dS) K / 8, dK = bf16(dS)^T Q / 8."""
+    qh, k, v = _xattn_qkv(q, kv, heads)
+    B, H, Sq, _ = qh.shape
+    dof = _f(do).reshape(B, Sq, H, 64).permute(0, 2, 1, 3)
+    of = _f(o).reshape(B, Sq, H, 64).permute(0, 2, 1, 3)
+    p = torch.exp((qh @ k.transpose(-1, -2)) * 0.125 - lse.unsqueeze(-1))
+    dv = _bfr(p).transpose(-1, -2) @ dof
+    ds = _bfr(p * (dof @ v.transpose(-1, -2) - (dof * of).sum(-1, keepdim=True)))
+    dq = ((ds @ k) * 0.125).permute(0, 2, 1, 3).reshape(q.shape)
+    dk = (ds.transpose(-1, -2) @ qh) * 0.125
+    dkv = torch.stack([dk, dv]).permute(1, 3, 0, 2, 4).reshape(kv.shape)
+    return dq.contiguous().to(q.dtype), dkv.contiguous().to(kv.dtype)
 
 
 def patchify(x, P):
