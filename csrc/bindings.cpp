@@ -827,6 +827,55 @@ std::vector<int64_t> xattn_plan(int64_t B, int64_t H, int64_t Sq, int64_t Sk) {
   return {p.tpw, p.walks, p.ws_floats};
 }
 
+// ------------------------------------------------------- neighbourhood attention (nattn.hip)
+// qkv [B Hf Wf, 3 H 32] bf16 contiguous rows in token order, rpb H * 169 floats.  Anything the
+// kernels do not serve is refused here, before an output exists.
+static mpa::NattnGeom nattn_geom(const char* op, const Tensor& qkv, const Tensor& rpb, int64_t heads,
+                                 int64_t Hf, int64_t Wf) {
+  CHECK_ACT(qkv);
+  TORCH_CHECK(qkv.dim() == 2 && heads > 0 && heads < 65536, op, ": qkv must be [B Hf Wf, 3 H 32] with heads");
+  TORCH_CHECK(Hf > 0 && Wf > 0 && Hf < 65536 && Wf < 65536, op, ": map out of range");
+  TORCH_CHECK(qkv.size(1) % (3 * heads) == 0, op, ": last dimension must be 3 * heads * 32, got ",
+              qkv.size(1));
+  TORCH_CHECK(qkv.numel() > 0 && qkv.numel() < ((int64_t)1 << 31), op, ": empty or too large (2^31 elements)");
+  TORCH_CHECK(qkv.size(0) % (Hf * Wf) == 0 && qkv.size(0) / (Hf * Wf) < 65536, op,
+              ": rows must be a multiple of Hf * Wf (at most 65535 images)");
+  const mpa::NattnGeom g{(int)(qkv.size(0) / (Hf * Wf)), (int)heads, (int)Hf, (int)Wf};
+  const char* err = mpa::nattn_geom_error(g, (int)(qkv.size(1) / (3 * heads)));
+  TORCH_CHECK(!err, op, ": ", err);
+  TORCH_CHECK(aligned16(qkv), op, ": qkv must be 16-byte aligned");
+  TORCH_CHECK(rpb.defined() && rpb.numel() == heads * mpa::NA_NB, op, ": rpb must hold heads * 169 floats");
+  TORCH_CHECK(fopt(rpb) != nullptr, op, ": rpb must be float32");
+  return g;
+}
+
+std::vector<Tensor> na_fwd(Tensor qkv, Tensor rpb, int64_t heads, int64_t Hf, int64_t Wf) {
+  const mpa::NattnGeom g = nattn_geom("na_fwd", qkv, rpb, heads, Hf, Wf);
+  const c10::OptionalDeviceGuard guard(device_of(qkv));
+  Tensor o = empty_like_shape(qkv, {qkv.size(0), (int64_t)g.H * mpa::NA_D}, torch::kBFloat16);
+  Tensor lse = empty_like_shape(qkv, {g.B, g.H, g.Hf * g.Wf}, torch::kFloat32);
+  mpa::nattn_fwd(bp(qkv), rpb.data_ptr<float>(), g, bpm(o), lse.data_ptr<float>(), cur_stream());
+  return {o, lse};
+}
+
+Tensor na_bwd(Tensor d_o, Tensor qkv, Tensor lse, Tensor rpb, Tensor drpb, int64_t heads, int64_t Hf,
+              int64_t Wf, bool overwrite) {
+  const mpa::NattnGeom g = nattn_geom("na_bwd", qkv, rpb, heads, Hf, Wf);
+  CHECK_ACT(d_o);
+  TORCH_CHECK(d_o.numel() == qkv.numel() / 3 && aligned16(d_o), "na_bwd: do must be [B Hf Wf, H 32]");
+  TORCH_CHECK(has(lse) && lse.numel() == (int64_t)g.B * g.H * g.Hf * g.Wf, "na_bwd: lse must be [B, H, Hf Wf]");
+  const float* lp = fopt(lse);
+  TORCH_CHECK(drpb.defined() && drpb.numel() == rpb.numel(), "na_bwd: drpb must match rpb");
+  float* dbp = fopt_mut(drpb);
+  const c10::OptionalDeviceGuard guard(device_of(qkv));
+  Tensor dqkv = torch::empty_like(qkv);
+  Tensor ws_t;
+  float* wsp = alloc_ws(ws_t, qkv, mpa::nattn_ws_floats(g));
+  mpa::nattn_bwd(bp(d_o), bp(qkv), lp, rpb.data_ptr<float>(), g, bpm(dqkv), dbp, overwrite, wsp,
+                 cur_stream());
+  return dqkv;
+}
+
 // ------------------------------------------------------ shifted-window attention (wattn.hip)
 // qkv [B Hf Wf, 3 H 32] bf16 contiguous rows in token order, bias H (2 ws - 1)^2 floats.
 // Anything the kernels do not serve is refused here, before an output exists.
@@ -2795,6 +2844,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("lse"), py::arg("heads"), "(dq, dkv) in q's and kv's layouts");
   m.def("xattn_plan", &xattn_plan, py::arg("B"), py::arg("H"), py::arg("Sq"), py::arg("Sk"),
         "(tiles per walk, walks, workspace floats) of xattn_fwd / xattn_bwd");
+  m.def("na_fwd", &na_fwd, py::arg("qkv"), py::arg("rpb"), py::arg("heads"), py::arg("Hf"), py::arg("Wf"));
+  m.def("na_bwd", &na_bwd, py::arg("do"), py::arg("qkv"), py::arg("lse"), py::arg("rpb"), py::arg("drpb"),
+        py::arg("heads"), py::arg("Hf"), py::arg("Wf"), py::arg("overwrite") = false);
   m.def("wattn_fwd", &wattn_fwd, py::arg("qkv"), py::arg("bias"), py::arg("heads"), py::arg("Hf"),
         py::arg("Wf"), py::arg("ws"), py::arg("shift"),
         "(o, lse): shifted-window attention over the rows qkv [B Hf Wf, 3 H 32] in token order");

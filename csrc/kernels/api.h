@@ -15,6 +15,7 @@
 #include "attn_plan.h"
 #include "wattn_plan.h"
 #include "xattn_plan.h"
+#include "nattn_plan.h"
 
 namespace mpa {
 
@@ -182,6 +183,20 @@ void xattn_fwd(const bf16_raw* q, const bf16_raw* kv, const XattnGeom& g, bf16_r
 int64_t xattn_ws_floats(const XattnGeom& g);
 void xattn_bwd(const bf16_raw* d_o, const bf16_raw* q, const bf16_raw* kv, const bf16_raw* o,
                const float* lse, const XattnGeom& g, bf16_raw* dq, bf16_raw* dkv, float* ws,
+               hipStream_t s);
+
+// nattn.hip: neighbourhood attention over the in-projection's rows qkv [B Hf Wf][3][H][32] bf16 in
+// natural token order (nattn_geom_error(g) == nullptr), planned by nattn_plan.h:
+// softmax(q k^T 32^-1/2 + rpb[h][yj - yi + 6][xj - xi + 6]) v over the 7 x 7 keys whose start is
+// clamped to the map.  rpb [H][13][13] fp32.  o [B Hf Wf][H 32] bf16, lse [B][H][Hf Wf] fp32.
+void nattn_fwd(const bf16_raw* qkv, const float* rpb, const NattnGeom& g, bf16_raw* o, float* lse,
+               hipStream_t s);
+// dqkv has qkv's layout and is written whole; drpb [H][169] is overwritten or accumulated.  ws
+// holds nattn_ws_floats(g) floats (delta, then the slab rows).  No float atomics: a dQ kernel
+// and a dK / dV kernel that recompute P from lse, then a fixed-order sum of the slab rows.
+int64_t nattn_ws_floats(const NattnGeom& g);
+void nattn_bwd(const bf16_raw* d_o, const bf16_raw* qkv, const float* lse, const float* rpb,
+               const NattnGeom& g, bf16_raw* dqkv, float* drpb, bool overwrite, float* ws,
                hipStream_t s);
 
 // wattn.hip: shifted-window attention over the in-projection's rows qkv [B Hf Wf][3][H][32] bf16

@@ -22,7 +22,7 @@ from typing import Any, Dict, List, Optional
 
 MODEL_NAMES = ("resnet18", "resnet34", "alexnet", "vgg", "vgg16", "squeezenet",
                "densenet", "inception", "mnasnet", "mobilenet_v3", "resnext50",
-               "convnext", "vit", "swin", "swin_v2", "pvt_v2")
+               "convnext", "vit", "swin", "swin_v2", "pvt_v2", "nat")
 
 _ENV_PREFIX = "MPA_"
 

@@ -34,6 +34,7 @@ from .convnext import convnext_tiny, ConvNeXt
 from .vit import vit_b_16, VisionTransformer
 from .swin import swin_t, swin_v2_t, SwinTransformer
 from .pvt import pvt_v2_b2, PyramidVisionTransformerV2
+from .nat import nat_mini, NAT
 
 ARCH = {
     "resnet18": ("resnet18", resnet18, 224),
@@ -90,6 +91,11 @@ PYRAMID_ARCH = {
     "pvt_v2": ("pvt_v2_b2", pvt_v2_b2, 224),
 }
 
+# Architectures on the neighbourhood attention kernels (nattn.hip), looked up after PYRAMID_ARCH.
+NEIGHBORHOOD_ARCH = {
+    "nat": ("nat_mini", nat_mini, 224),
+}
+
 
 def set_parameter_requires_grad(model: nn.Module, feature_extracting: bool) -> None:
     if feature_extracting:
@@ -113,7 +119,8 @@ def initialize_model(model_name: str, num_classes: int, feature_extract: bool,
     entry = (ARCH.get(model_name) or EXTRA_ARCH.get(model_name) or SE_ARCH.get(model_name)
              or GROUPED_ARCH.get(model_name) or LN_ARCH.get(model_name)
              or ATTN_ARCH.get(model_name) or WINDOW_ARCH.get(model_name)
-             or WINDOW_V2_ARCH.get(model_name) or PYRAMID_ARCH.get(model_name))
+             or WINDOW_V2_ARCH.get(model_name) or PYRAMID_ARCH.get(model_name)
+             or NEIGHBORHOOD_ARCH.get(model_name))
     if entry is None:
         raise ValueError("Invalid model name {!r}".format(model_name))
     arch, ctor, input_size = entry
@@ -140,7 +147,7 @@ def initialize_model(model_name: str, num_classes: int, feature_extract: bool,
         model.classifier[2] = Linear(model.classifier[2].in_features, num_classes)
     elif model_name == "vit":
         model.heads.head = Linear(model.heads.head.in_features, num_classes)
-    elif model_name in ("swin", "swin_v2", "pvt_v2"):
+    elif model_name in ("swin", "swin_v2", "pvt_v2", "nat"):
         model.head = Linear(model.head.in_features, num_classes)
     return model, input_size
 
@@ -165,7 +172,7 @@ def head_parameters(model: nn.Module):
 
 
 __all__ = ["initialize_model", "set_parameter_requires_grad", "ARCH", "EXTRA_ARCH", "SE_ARCH",
-           "GROUPED_ARCH", "LN_ARCH", "ATTN_ARCH", "WINDOW_ARCH", "WINDOW_V2_ARCH", "PYRAMID_ARCH", "convnext_tiny", "vit_b_16", "swin_t", "swin_v2_t", "pvt_v2_b2", "InceptionOutputs", "mnasnet1_0", "mobilenet_v3_large",
+           "GROUPED_ARCH", "LN_ARCH", "ATTN_ARCH", "WINDOW_ARCH", "WINDOW_V2_ARCH", "PYRAMID_ARCH", "NEIGHBORHOOD_ARCH", "nat_mini", "convnext_tiny", "vit_b_16", "swin_t", "swin_v2_t", "pvt_v2_b2", "InceptionOutputs", "mnasnet1_0", "mobilenet_v3_large",
            "resnext50_32x4d",
            "input_spec",
            "resnet18", "resnet34", "vgg11_bn", "vgg16", "alexnet", "squeezenet1_0",

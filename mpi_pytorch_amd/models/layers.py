@@ -555,6 +555,32 @@ class ShiftedWindowAttention(nn.Module):
                                                                   self.num_heads)
 
 
+class NeighborhoodAttention(nn.Module):
+    """NAT's attention with the official names: ``qkv``, ``rpb`` [heads, 13, 13] and ``proj``.
+    Head dim 32, neighbourhood 7.  The in-projection's rows [B Hf Wf, 3 D] are the kernel's input
+    in natural token order and its output rows are the out-projection's input: the 49 keys of a
+    pixel are the kernel's address arithmetic, the bias gather its register arithmetic."""
+
+    def __init__(self, dim: int, num_heads: int):
+        super().__init__()
+        if dim != 32 * num_heads:
+            raise ValueError("NeighborhoodAttention: head dim must be 32 (dim = 32 * num_heads)")
+        self.dim, self.num_heads = dim, num_heads
+        self.qkv = Linear(dim, 3 * dim)
+        self.rpb = nn.Parameter(nn.init.trunc_normal_(torch.empty(num_heads, 13, 13), std=0.02))
+        self.proj = Linear(dim, dim)
+
+    def forward(self, rows, Hf: int, Wf: int):
+        """rows [B Hf Wf, D] -> [B Hf Wf, D]"""
+        qkv = Fn.linear_act(rows, self.qkv)
+        if not qkv.is_contiguous():
+            qkv = qkv.contiguous()
+        return Fn.linear_act(Fn.neighborhood_attention(qkv, self.rpb, self.num_heads, Hf, Wf), self.proj)
+
+    def extra_repr(self):
+        return "dim={}, num_heads={}".format(self.dim, self.num_heads)
+
+
 class SpatialReductionAttention(nn.Module):
     """PVT v2's attention with the official names: ``q``, ``kv``, ``proj`` and, where ``sr_ratio``
     > 1, the reduction ``sr`` (a conv with kernel = stride = sr_ratio, run as ``Fn.patch_rows`` and

@@ -1276,6 +1276,37 @@ def window_attention(qkv, bias, heads: int, Hf: int, Wf: int, ws: int, shift: in
     return K(qkv).wattn_fwd(qkv, bias, heads, Hf, Wf, ws, shift)[0]
 
 
+class _NeighborhoodAttention(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, qkv, rpb, heads, Hf, Wf):
+        o, lse = K(qkv).na_fwd(qkv, rpb, heads, Hf, Wf)
+        ctx.rpb, ctx.geom = rpb, (heads, Hf, Wf)
+        ctx.save_for_backward(qkv, lse)
+        return o
+
+    @staticmethod
+    def backward(ctx, do):
+        qkv, lse = ctx.saved_tensors
+        rpb, k = ctx.rpb, K(do)
+        do = do.contiguous()
+        if not rpb.requires_grad:  # frozen: the bias gradient into scratch
+            tmp = torch.empty(rpb.numel(), device=do.device, dtype=torch.float32)
+            return _grads(_NeighborhoodAttention, k.na_bwd(do, qkv, lse, rpb, tmp, *ctx.geom, True))
+        dqkv = k.na_bwd(do, qkv, lse, rpb, grad_sink(rpb), *ctx.geom, _fresh(rpb))
+        _done(rpb)
+        return _grads(_NeighborhoodAttention, dqkv)
+
+
+def neighborhood_attention(qkv, rpb, heads: int, Hf: int, Wf: int):
+    """NAT's attention over the in-projection's rows ``qkv`` [B Hf Wf, 3 * heads * 32] in natural
+    token order: every pixel attends the 7 x 7 neighbourhood centred on it (clamped to the map, so
+    always 49 keys), softmax(q k^T / sqrt(32) + rpb[h][dy + 6][dx + 6]) v; ``rpb`` holds heads * 169
+    floats.  Returns rows [B Hf Wf, heads * 32]: no gathered key or value tensor exists."""
+    if torch.is_grad_enabled() and (qkv.requires_grad or rpb.requires_grad):
+        return _NeighborhoodAttention.apply(qkv, rpb, heads, Hf, Wf)
+    return K(qkv).na_fwd(qkv, rpb, heads, Hf, Wf)[0]
+
+
 class _WindowAttentionCos(torch.autograd.Function):
     @staticmethod
     def forward(ctx, qkv, bias, logit_scale, heads, Hf, Wf, ws, shift):

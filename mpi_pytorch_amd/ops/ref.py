@@ -460,6 +460,76 @@ def wattn_bwd(do, qkv, lse, bias, dbias, heads, Hf, Wf, ws, shift, overwrite=Fal
     return window_reverse(w, Hf, Wf, ws, shift).contiguous().to(qkv.dtype)
 
 
+# ------------------------------------------------------------ neighbourhood attention (NAT)
+_NA_TABLES = {}
+
+
+def na_tables(Hf, Wf):
+    """(key index [Hf Wf, 49], bias index [Hf Wf, 49]) int64 of the definition, by a plain loop:
+    query (yi, xi) attends rows ni(yi) .. ni(yi) + 6 and columns ni(xi) .. ni(xi) + 6 with
+    ni(i) = min(max(i - 3, 0), L - 7), bias index (yj - yi + 6) * 13 + (xj - xi + 6)."""
+    if (Hf, Wf) not in _NA_TABLES:
+        ni = lambda i, L: min(max(i - 3, 0), L - 7)
+        keys, rel = [], []
+        for yi in range(Hf):
+            for xi in range(Wf):
+                ys, xs = range(ni(yi, Hf), ni(yi, Hf) + 7), range(ni(xi, Wf), ni(xi, Wf) + 7)
+                keys.append([yj * Wf + xj for yj in ys for xj in xs])
+                rel.append([(yj - yi + 6) * 13 + (xj - xi + 6) for yj in ys for xj in xs])
+        _NA_TABLES[(Hf, Wf)] = (torch.tensor(keys), torch.tensor(rel))
+    return _NA_TABLES[(Hf, Wf)]
+
+
+def _na_operands(qkv, rpb, heads, Hf, Wf):
+    """q [B, H, N, 32], gathered k, v [B, H, N, 49, 32] fp32, the additive term [1, H, N, 49] and
+    the two index tables."""
+    if qkv.dim() != 2 or heads < 1 or not qkv.is_contiguous():
+        raise ValueError("neighbourhood attention: qkv must be contiguous rows [B Hf Wf, 3 H 32]")
+    if not qkv.is_floating_point() or qkv.dtype == torch.float64 or rpb.dtype != torch.float32:
+        raise ValueError("neighbourhood attention: qkv must be bf16 (fp32 on the CPU path), rpb fp32")
+    if qkv.shape[1] != 3 * heads * 32:
+        raise ValueError("neighbourhood attention: head dim must be 32")
+    if Hf < 7 or Wf < 7:
+        raise ValueError("neighbourhood attention: the map must be at least 7 x 7")
+    if qkv.shape[0] == 0 or qkv.shape[0] % (Hf * Wf) or rpb.numel() != heads * 169:
+        raise ValueError("neighbourhood attention: rows a multiple of Hf Wf, rpb H * 169 floats")
+    kidx, bidx = (t.to(qkv.device) for t in na_tables(Hf, Wf))
+    q, k, v = _f(qkv).reshape(-1, Hf * Wf, 3, heads, 32).permute(2, 0, 3, 1, 4)
+    add = rpb.reshape(heads, 169)[:, bidx].unsqueeze(0)
+    return q, k[:, :, kidx], v[:, :, kidx], add, kidx, bidx
+
+
+def na_fwd(qkv, rpb, heads, Hf, Wf):
+    """(o [B Hf Wf, H 32], lse [B, H, Hf Wf]): softmax(q k^T 32^-1/2 + rpb) v over each query's 49
+    keys; fp32 scores and statistics, P a bf16 operand, the row sum unrounded."""
+    q, kg, vg, add, _, _ = _na_operands(qkv, rpb, heads, Hf, Wf)
+    s = torch.einsum("bhnd,bhnjd->bhnj", q, kg) * WATTN_SCALE + add
+    m = s.amax(-1, keepdim=True)
+    p = torch.exp(s - m)
+    l = p.sum(-1, keepdim=True)
+    o = torch.einsum("bhnj,bhnjd->bhnd", _bfr(p), vg) / l
+    return o.permute(0, 2, 1, 3).reshape(-1, heads * 32).to(qkv.dtype), (m + torch.log(l)).squeeze(-1)
+
+
+def na_bwd(do, qkv, lse, rpb, drpb, heads, Hf, Wf, overwrite=False):
+    """dqkv in qkv's layout, drpb (+)= the fp32 sum of the unrounded dS over the entries of each
+    bias index; P, delta, dS and the bf16 operands as in ``wattn_bwd``."""
+    q, kg, vg, add, kidx, bidx = _na_operands(qkv, rpb, heads, Hf, Wf)
+    B, N = q.shape[0], Hf * Wf
+    dof = _f(do).reshape(B, N, heads, 32).permute(0, 2, 1, 3)
+    p = torch.exp(torch.einsum("bhnd,bhnjd->bhnj", q, kg) * WATTN_SCALE + add - lse.unsqueeze(-1))
+    dp = torch.einsum("bhnd,bhnjd->bhnj", dof, vg)
+    ds = p * (dp - (p * dp).sum(-1, keepdim=True))
+    dq = torch.einsum("bhnj,bhnjd->bhnd", _bfr(ds), kg) * WATTN_SCALE
+    scatter = lambda w, x: torch.zeros_like(q).index_add_(
+        2, kidx.reshape(-1), (w.unsqueeze(-1) * x.unsqueeze(3)).reshape(B, heads, N * 49, 32))
+    dk, dv = scatter(_bfr(ds), q) * WATTN_SCALE, scatter(_bfr(p), dof)
+    db = torch.zeros(heads, 169, device=qkv.device)
+    db.index_add_(1, bidx.reshape(-1), ds.sum(0).reshape(heads, N * 49))
+    _acc(drpb.reshape(heads, -1), db, overwrite)
+    return torch.stack([dq, dk, dv]).permute(1, 3, 0, 2, 4).reshape(B * N, 3 * heads * 32).to(qkv.dtype)
+
+
 # ------------------------------------------- cosine window attention and position bias (Swin V2)
 WATTN_LOGIT_MAX = math.log(100.0)  # the clamp of logit_scale: a temperature of at most 100
 
